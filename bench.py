@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): p50 reconcile-to-Ready latency + readyReplicas accuracy
-at replicas = 1/2/4/8, plus the scale-down (config 4) and two-pool (config 5) numbers.
+at replicas = 1/2/4/8, plus, with ``--full``, the scale-down (config 4) and two-pool (config 5)
+numbers.
 
 Timed region — ``--steps K`` steps, each one a replica sweep of one ``Mi355xPool`` on one node:
   for n in {1, 2, 4, 8} ∩ [1, N] (and N itself):
@@ -16,7 +17,20 @@ Timed region — ``--steps K`` steps, each one a replica sweep of one ``Mi355xPo
   The amd-smi CLI read (~0.7 s on hardware) happens once per step and is reported separately
   (``ground_truth_ms_per_step``) so ``operator_ms_per_step`` is the control plane's own time.
 
-After the timed region (not part of ms_per_step):
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs: set-up, warm-up,
+the K timed steps, ``--dump-outputs`` if asked for, and the JSON line (``value``, ``ms_per_step``,
+``per_n`` with its accuracy and device evidence). ``--steps`` is the number of timed steps: a plain
+run has no wall budget unless ``--budget-s`` sets one. Everything below is measured only with
+``--full``, which also adds the diagnostics that take requests of their own (agent / manager
+footprint, the agent's counters, the manager's reconcile traces and the latency split from them).
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step — for every point of
+the sweep the pool status its caller received at Ready and the ground truth read beside it — as
+``DIR/<name>.npy`` (float64; see ``_dump_outputs``). Only computed values are written (replica
+counts, device health, probe verdicts and CU census counts), no timings or bandwidths, so two builds
+run with the same arguments can be compared output for output.
+
+With ``--full``, after the timed region (not part of ms_per_step):
   * config 4: ``--scale-down-steps`` x (N GPUs each running a pod -> replicas N//2, timed until
     the pool is Ready at N//2 with the victims' pods evicted and the GPUs released);
   * config 5: ``--pool-steps`` x two pools of N//2 created together, timed until both are Ready,
@@ -26,19 +40,22 @@ After the timed region (not part of ms_per_step):
     amdsmi event takes) — and reaction only (forced sample).
 
 ``value`` is the p50 reconcile-to-Ready latency at replicas = N (``--gpus``), the largest point of
-the sweep; ``per_n`` holds every point, ``e2e_breakdown_p50_ms`` / ``claim_pass_span_p50_ms`` the
-median split of a cycle and ``slowest_cycle`` the same split for the slowest timed cycle. With N GPUs visible (real MI355X) the agent uses the
+the sweep; ``per_n`` holds every point, ``slowest_cycle`` the slowest timed cycle and, with
+``--full``, ``e2e_breakdown_p50_ms`` / ``claim_pass_span_p50_ms`` the median split of a cycle (and
+the same split for the slowest one). With N GPUs visible (real MI355X) the agent uses the
 amdsmi backend and the gfx950 HIP probe in per-GPU probe helpers; without GPUs it falls back to the 8-GPU fake fixture
 with a simulated probe, and says so in ``data``. The API server is always the in-repo apiserver
 simulator (no kube-apiserver/etcd in this environment).
 
 Launch contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 under
 ``torch.distributed.run`` every rank joins a gloo process group for the barriers and rank 0
-drives the control plane, which manages all GPUs of the node. The bench process itself issues no
-GPU work (the node agent, a child process, owns the GPUs), so there is no device stream to
-synchronise around the timed region. With N > 1 real GPUs, after the timed region and after the
-control plane has released every GPU, each rank all-reduces over its own GPU in a child process
-(RCCL over xGMI; ``config.rccl_allreduce``: exactness + bus bandwidth).
+drives the control plane, which manages all GPUs of the node. The bench process loads the native
+libraries the run stands on (``_load_native``; a missing one is an error, ``config.native`` names
+them) but issues no GPU work itself (the node agent, a child process, owns the GPUs), so there is
+no device stream to synchronise around the timed region. With ``--full`` and N > 1 real GPUs,
+after the timed region and after the control plane has released every GPU, each rank all-reduces
+over its own GPU in a child process (RCCL over xGMI; ``config.rccl_allreduce``: exactness + bus
+bandwidth).
 """
 from __future__ import annotations
 
@@ -186,6 +203,71 @@ def _window(traces: list[dict], t0: float, t1: float) -> list[dict]:
     return [t for t in traces if t0 <= t["start"] <= t1]
 
 
+def _dump_outputs(path: str, sweep: list[int], cycles: list[dict]) -> list[str]:
+    """``--dump-outputs``: the last timed cycle of every sweep point, as float64 ``.npy`` arrays.
+
+    One entry per sweep point (in sweep order):
+      sweep_replicas     the replicas asked for;
+      ready_replicas     status.readyReplicas of the pool the caller saw Ready (-1: no such cycle);
+      ready_condition    1 if that status carries Ready=True;
+      status_devices     len(status.devices);
+      truth_ready        the independent ground truth read at that instant;
+      accurate           1 if the two agreed (what ``readyReplicas_accuracy`` counts).
+    One entry per claimed GPU, the sweep points' devices one after another in status order:
+      device_healthy     1 if status.devices[i].health is "Healthy";
+      device_advertised  1 if the GPU is advertised to the kubelet;
+      probe_passed       the claim-time probe's verdict (HBM pattern test, MFMA GEMM + ABFT);
+      probe_cus_expected / probe_cus_verified   the CU census: compute units the GPU has and
+                         those whose matrix cores proved themselves (-1: census not reported).
+    Timings and bandwidths are left out: they are measurements, not results."""
+    import numpy as np
+    last = {cy["n"]: cy for cy in cycles}  # the latest cycle of each N wins
+    per_point: dict[str, list[float]] = {k: [] for k in (
+        "sweep_replicas", "ready_replicas", "ready_condition", "status_devices", "truth_ready",
+        "accurate")}
+    fields = (("probe_passed", "passed"), ("probe_cus_expected", "cusExpected"),
+              ("probe_cus_verified", "cusVerified"))
+    per_dev: dict[str, list[float]] = {name: [] for name in (
+        "device_healthy", "device_advertised", *(f for f, _ in fields))}
+    for k in sweep:
+        cy = last.get(k)
+        st = (cy or {}).get("status") or {}
+        per_point["sweep_replicas"].append(k)
+        per_point["ready_replicas"].append(st.get("readyReplicas", -1) if cy else -1)
+        per_point["ready_condition"].append(int(any(
+            c.get("type") == "Ready" and c.get("status") == "True"
+            for c in st.get("conditions") or [])))
+        per_point["status_devices"].append(len(st.get("devices") or []))
+        per_point["truth_ready"].append(((cy or {}).get("truth") or {}).get("ready", -1))
+        per_point["accurate"].append(int(bool((cy or {}).get("ok"))))
+        for d in st.get("devices") or []:
+            per_dev["device_healthy"].append(int(d.get("health") == "Healthy"))
+            per_dev["device_advertised"].append(int(bool(d.get("advertised"))))
+            for name, key in fields:
+                v = (d.get("probe") or {}).get(key)
+                per_dev[name].append(-1 if v is None else float(v))
+    os.makedirs(path, exist_ok=True)
+    for name, vals in {**per_point, **per_dev}.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(vals, dtype=np.float64))
+    return sorted({**per_point, **per_dev})
+
+
+def _load_native(real: bool) -> dict:
+    """Load the native libraries this run stands on into this process, before any child starts,
+    and name them in the result: libmi355x_dev.so (both device backends, the health verdicts and
+    GPU selection the agent calls) and, on real GPUs, libmi355x_probe.so with its gfx950 kernels.
+    A library that is missing or does not load ends the run here with its error — with GPUs
+    visible the bench never falls back to the simulated probe — instead of surfacing as a claim
+    that times out inside a probe helper. Loading initialises no HIP device in this process: the
+    GPU work stays with the agent's helpers."""
+    from gpupool.ops import devlib, probe
+    out = {"libmi355x_dev": devlib.version()}
+    if real:
+        probe.lib()
+        out["libmi355x_probe"] = "loaded (gfx950 probe kernels; devices initialised by the helpers)"
+    return out
+
+
 def main() -> int:
     t_main = time.monotonic()
     ap = argparse.ArgumentParser()
@@ -198,9 +280,16 @@ def main() -> int:
     ap.add_argument("--workdir", default="")
     ap.add_argument("--keep", action="store_true", help="keep the workdir (logs)")
     ap.add_argument("--timeout", type=float, default=120.0, help="per-transition timeout (s)")
-    ap.add_argument("--budget-s", type=float, default=480.0,
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary scenarios (scale-down, two "
+                         "pools, AzureVmPool, health latency, accuracy under faults, the N>1 "
+                         "collective check) and collect the footprint / trace diagnostics")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--budget-s", type=float, default=0.0,
                     help="wall budget for the whole run (s): work not started by then is skipped "
-                         "and reported as such; the JSON line is always printed")
+                         "and reported as such; the JSON line is always printed (default: 480 "
+                         "with --full, none for a plain run, so --steps sets the timed steps)")
     ap.add_argument("--sample-interval", type=float, default=1.0,
                     help="agent full-telemetry sample period (s)")
     ap.add_argument("--scale-down-steps", type=int, default=3, help="config 4 repetitions (0 = skip)")
@@ -224,18 +313,22 @@ def main() -> int:
                     help="fault injection: COUNT:SECONDS — the agent stalls every claim of >= "
                          "COUNT GPUs (exercises the bench's failure isolation)")
     args = ap.parse_args()
-    deadline = t_main + args.budget_s
+    if not args.full:  # a plain run: the headline only
+        args.scale_down_steps = args.pool_steps = args.azure_steps = 0
+        args.health_steps = args.fault_steps = 0
+        args.comm_check = "off"
+    budget_s = args.budget_s or (480.0 if args.full else 0.0)
+    deadline = t_main + budget_s if budget_s else 0.0  # 0: no wall budget
 
     def budget_left() -> float:
-        return deadline - time.monotonic()
+        return deadline - time.monotonic() if deadline else float("inf")
 
     rank, world = _dist_init()
     n = args.gpus
     sweep = sweep_for(n)
     visible = _visible_gpus()
-    from gpupool.ops import native_dir
-    have_probe = os.path.exists(os.path.join(native_dir(), "libmi355x_probe.so"))
-    real = args.backend == "real" or (args.backend == "auto" and visible >= n and have_probe)
+    real = args.backend == "real" or (args.backend == "auto" and visible >= n)
+    native = _load_native(real)
 
     cluster = run = pool = None
     cycles: list[dict] = []
@@ -296,7 +389,7 @@ def main() -> int:
     gc.collect()
     gc.freeze()
     _barrier(world)
-    footprint_before = run.footprint() if rank == 0 and run else {}
+    footprint_before = run.footprint() if rank == 0 and run and args.full else {}
     t_start = time.perf_counter()
     last_progress = t_start
     # the manager keeps its last 4096 reconcile traces: a long run collects them as it goes (between
@@ -317,7 +410,7 @@ def main() -> int:
         for step in range(args.steps):
             if budget_left() <= 0:
                 skipped["timed_steps"] = f"{args.steps - step} of {args.steps} not started: " \
-                                         f"wall budget ({args.budget_s:.0f} s) exhausted"
+                                         f"wall budget ({budget_s:.0f} s) exhausted"
                 break
             try:
                 run.refresh_health()
@@ -335,7 +428,7 @@ def main() -> int:
                     if not pool_ok:
                         break
             timed_steps += 1
-            if timed_steps % 100 == 0:
+            if args.full and timed_steps % 100 == 0:
                 harvest()
             if time.perf_counter() - last_progress > 20.0:  # a long run shows it is alive
                 last_progress = time.perf_counter()
@@ -347,13 +440,15 @@ def main() -> int:
                 break
     _barrier(world)
     elapsed = _gather_max(world, time.perf_counter() - t_start)
-    footprint_after = run.footprint() if rank == 0 and run else {}
+    footprint_after = run.footprint() if rank == 0 and run and args.full else {}
 
     if rank == 0:
         from gpupool.bench.runner import summary
         gt_s = run.gt_s if run else 0.0
 
         def traces_now() -> list:
+            if not args.full:
+                return []
             try:
                 return cluster.manager_traces(n=2048)
             except Exception:
@@ -475,11 +570,11 @@ def main() -> int:
             if fa:
                 secondary["accuracy_under_faults"].update(fa[0])
         try:
-            agent_stats = run.agent_stats() if run else {}
+            agent_stats = run.agent_stats() if run and args.full else {}
         except Exception as e:
             agent_stats = {"error": repr(e)}
         try:
-            metrics = cluster.manager_metrics()
+            metrics = cluster.manager_metrics() if args.full else ""
         except Exception:
             metrics = ""
         all_traces = traces_now()
@@ -609,14 +704,23 @@ def main() -> int:
                 "claim_pass_span_p50_ms_per_n": span_per_n,
                 "e2e_breakdown_p50_ms": e2e_p50,
                 "slowest_cycle": slowest,
-                "budget": {"budget_s": args.budget_s,
+                "budget": {"budget_s": budget_s,
                            "used_s": round(time.monotonic() - t_main, 2),
                            "skipped": skipped},
                 "steps_detail": [{k2: (round(v, 4) if isinstance(v, float) else v)
-                                  for k2, v in cy.items() if k2 not in ("patchAt", "readyAtWall")}
+                                  for k2, v in cy.items()
+                                  if k2 not in ("patchAt", "readyAtWall", "status")}
                                  for cy in cycles[:len(sweep)]],
             },
         }
+        out["config"]["full"] = args.full
+        out["config"]["native"] = native
+        if not args.full:  # what only --full collects is left out, not reported empty
+            for k in ("health_condition_latency", "agent", "footprint", "claim_pass_span_p50_ms",
+                      "claim_pass_span_p50_ms_per_n", "e2e_breakdown_p50_ms", "trace_harvest_s"):
+                out["config"].pop(k, None)
+        if args.dump_outputs:
+            out["config"]["dumped_outputs"] = _dump_outputs(args.dump_outputs, sweep, cycles)
         if setup_error is not None:
             out["config"]["setup_error"] = setup_error
         for k in ("ground_truth",):

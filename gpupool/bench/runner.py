@@ -204,6 +204,7 @@ class BenchRun:
         self.phase = "release"
         self.scale(name, 0)
         return {"n": n, "readySeconds": t_ready, "ok": ok, "truth": truth,
+                "status": obj["status"],  # what the caller of the timed path received
                 "truthFirstReadAgrees": truth["firstReadAgrees"],
                 "indices": [d.get("index") for d in obj["status"]["devices"]],
                 "patchAt": patch_at, "readyAtWall": ready_at_wall, "patchRttMs": patch_rtt * 1e3,

@@ -25,7 +25,7 @@ PY = sys.executable
 
 
 def _bench(*extra: str) -> list[str]:
-    return [PY, "-u", "bench.py", *extra]
+    return [PY, "-u", "bench.py", "--full", *extra]  # secondary scenarios + diagnostics too
 
 
 def _prof(tag_dir: str, name: str, *cmd: str, pmc: tuple[str, ...] = ()) -> list[str]:
@@ -58,7 +58,7 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         "sharing": [("pytest_sharing", pytest + ["tests/gpu/test_sharing_gpu.py"], 400, {}),
                     ("slot_interference", [PY, "scripts/slot_interference_ab.py"], 300, {}),
                     ("cu_mask_layouts", [PY, "scripts/cu_mask_layouts.py"], 200, {})],
-        # the headline (BASELINE config 2) as the driver runs it
+        # the headline (BASELINE config 2) and, with --full, the secondary scenarios behind it
         "bench": [("bench", _bench("--steps", "20", "--warmup", "3"), 300, {})],
         "soak": [("bench_soak300", _bench("--steps", "300", "--warmup", "3"), 900, {})],
         "soak600": [("bench_soak600", _bench("--steps", "600", "--warmup", "3", "--budget-s",
@@ -72,7 +72,7 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # bench sat silent until the box's 180 s hang guard), and the kernels are the same ones
         # (helper vs inproc bench A/B: profiles/r5c_bench_helper_vs_inproc_ab.json)
         "prof": [("bench_prof", _prof(tag_dir, "bench_prof", PY, os.path.join(ROOT, "bench.py"),
-                                      "--gpus", "1", "--steps", "10", "--warmup", "2",
+                                      "--full", "--gpus", "1", "--steps", "10", "--warmup", "2",
                                       "--health-steps", "0", "--probe-mode", "inproc"), 400, {})],
         # counters of the probe GEMM (one pass: 4 TCC counters at most per run)
         "pmc": [(f"gemm_l2_g{g}", _prof(tag_dir, f"gemm_l2_g{g}", PY,

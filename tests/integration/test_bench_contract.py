@@ -24,8 +24,9 @@ def run_bench(*args: str, timeout: float = 600) -> dict:
 
 
 def test_bench_gpus8_sweep_scale_down_two_pools(native_built):
-    out = run_bench("--gpus", "8", "--steps", "1", "--warmup", "0", "--scale-down-steps", "1",
-                    "--pool-steps", "1", "--health-steps", "1", "--fault-steps", "20")
+    out = run_bench("--full", "--gpus", "8", "--steps", "1", "--warmup", "0",
+                    "--scale-down-steps", "1", "--pool-steps", "1", "--health-steps", "1",
+                    "--fault-steps", "20")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
               "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in out
@@ -108,7 +109,7 @@ def test_bench_isolates_a_hung_n8_and_keeps_the_curve(native_built):
     per_n 1/2/4 are measured, N=8 carries the error and its phase, ``value`` falls back to the
     largest N that completed (and says so), the pool is recovered and the secondary scenarios
     still run (scale-down, which needs 8 GPUs, records its own error)."""
-    out = run_bench("--gpus", "8", "--steps", "2", "--warmup", "0", "--timeout", "4",
+    out = run_bench("--full", "--gpus", "8", "--steps", "2", "--warmup", "0", "--timeout", "4",
                     "--inject-claim-hang", "8:12", "--scale-down-steps", "1", "--pool-steps", "1",
                     "--health-steps", "0", "--fault-steps", "0", "--azure-steps", "1",
                     timeout=400)
@@ -125,7 +126,7 @@ def test_bench_isolates_a_hung_n8_and_keeps_the_curve(native_built):
 
 
 def test_bench_wall_budget_always_prints_json(native_built):
-    out = run_bench("--gpus", "2", "--steps", "50", "--warmup", "0", "--budget-s", "1",
+    out = run_bench("--full", "--gpus", "2", "--steps", "50", "--warmup", "0", "--budget-s", "1",
                     "--scale-down-steps", "1", "--pool-steps", "1", "--health-steps", "1")
     cfg = out["config"]
     assert out["value"] is None and out["status"] == "failed"
@@ -135,8 +136,8 @@ def test_bench_wall_budget_always_prints_json(native_built):
 
 
 def test_bench_gpus1_contract(native_built):
-    out = run_bench("--gpus", "1", "--steps", "2", "--warmup", "0", "--scale-down-steps", "1",
-                    "--pool-steps", "1", "--health-steps", "0")
+    out = run_bench("--full", "--gpus", "1", "--steps", "2", "--warmup", "0",
+                    "--scale-down-steps", "1", "--pool-steps", "1", "--health-steps", "0")
     cfg = out["config"]
     assert list(cfg["per_n"]) == ["1"] and out["value"] == cfg["per_n"]["1"]["p50_s"]
     assert cfg["scale_down"]["from"] == 1 and cfg["scale_down"]["to"] == 0
@@ -156,8 +157,8 @@ def test_bench_under_torchrun_two_ranks_with_comm_check(native_built):
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node=2", "--master-addr=127.0.0.1", f"--master-port={port}",
-                        os.path.join(ROOT, "bench.py"), "--backend", "fake", "--gpus", "2",
-                        "--steps", "1", "--warmup", "0", "--scale-down-steps", "0",
+                        os.path.join(ROOT, "bench.py"), "--backend", "fake", "--full", "--gpus",
+                        "2", "--steps", "1", "--warmup", "0", "--scale-down-steps", "0",
                         "--pool-steps", "0", "--health-steps", "0", "--comm-check", "gloo"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT,
                        env=dict(os.environ, OMP_NUM_THREADS="2"))
@@ -169,3 +170,58 @@ def test_bench_under_torchrun_two_ranks_with_comm_check(native_built):
     comm = out["config"]["rccl_allreduce"]
     assert comm["world"] == 2 and comm["ranks_ok"] == 2 and comm["exact"], comm
     assert comm["min_busbw_GBps"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(native_built, tmp_path):
+    """Without ``--full`` the bench warms up, times exactly ``--steps`` steps and prints the result
+    line: no secondary scenario, no footprint / trace diagnostics, no wall budget cutting the steps
+    short. ``--dump-outputs`` writes what the last timed step returned, identically from run to
+    run."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        out = run_bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path / d))
+        runs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert out["unit"] == "s" and out["higher_is_better"] is False and out["dtype"] == "bf16"
+    assert out["status"] == "ok" and out["steps"] == 3 and out["ms_per_step"] > 0
+    cfg = out["config"]
+    assert cfg["full"] is False and cfg["timed_steps_completed"] == 3
+    # the bench process itself loaded the native device library it names (no GPU here: no probe)
+    assert cfg["native"]["libmi355x_dev"].startswith("mi355x_dev ") and \
+        "libmi355x_probe" not in cfg["native"]
+    assert cfg["budget"]["budget_s"] == 0 and not cfg["budget"]["skipped"]
+    assert sorted(cfg["per_n"], key=int) == ["1", "2"]
+    for k, v in cfg["per_n"].items():  # three timed cycles per sweep point, all accurate
+        assert v["n"] == 3 and v["accuracy"] == 1.0 and v["probe_ms_p50"] > 0, (k, v)
+    assert out["value"] == cfg["per_n"]["2"]["p50_s"] and cfg["readyReplicas_accuracy"] == 1.0
+    for k in ("scale_down", "two_pools", "azure_config1", "health_condition_latency",
+              "accuracy_under_faults", "rccl_allreduce", "footprint", "agent",
+              "claim_pass_span_p50_ms", "e2e_breakdown_p50_ms"):
+        assert k not in cfg, k
+    a, b = runs
+    assert sorted(a) == sorted(cfg["dumped_outputs"]) == sorted(b)
+    for name in a:
+        assert a[name].dtype == np.float64 and np.array_equal(a[name], b[name]), name
+    assert a["sweep_replicas"].tolist() == [1, 2] and a["ready_replicas"].tolist() == [1, 2]
+    assert a["truth_ready"].tolist() == [1, 2] and a["accurate"].tolist() == [1, 1]
+    assert a["ready_condition"].tolist() == [1, 1] and a["status_devices"].tolist() == [1, 2]
+    assert a["probe_passed"].tolist() == [1, 1, 1]  # one claimed GPU, then two
+    assert a["device_healthy"].tolist() == [1, 1, 1] == a["device_advertised"].tolist()
+    assert a["probe_cus_verified"].tolist() == a["probe_cus_expected"].tolist()
+    assert (a["probe_cus_expected"] > 0).all()
+
+
+def test_bench_without_its_native_libraries_is_an_error(native_built, tmp_path):
+    """A tree whose native libraries are absent does not bench anything: the run ends with the
+    loader's error and prints no result line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "fake",
+                        "--gpus", "1", "--steps", "1", "--warmup", "0"],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT,
+                       env=dict(os.environ, GPUPOOL_NATIVE_DIR=str(tmp_path)))
+    assert r.returncode != 0 and "NativeLibraryMissing" in r.stderr, r.stderr[-2000:]
+    assert "libmi355x_dev.so not found" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
