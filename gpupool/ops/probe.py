@@ -49,6 +49,12 @@ def lib() -> ctypes.CDLL:
             l.mi355x_probe_gemm_bf16.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int]
+            if hasattr(l, "mi355x_probe_gemm_bf16_opts"):  # absent from a library built before it
+                l.mi355x_probe_gemm_bf16_opts.restype = ctypes.c_int
+                l.mi355x_probe_gemm_bf16_opts.argtypes = [ctypes.c_int, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_char_p]
             _lib = l
     return _lib
 
@@ -82,9 +88,9 @@ def identify(dev: int) -> dict:
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
-    older register-staged kernel, for A/B). ``test_hooks``: injectBitFlips=N / injectGemmFault=1
-    corrupt the device buffers between compute and check so tests can prove the checkers catch
-    faults."""
+    older register-staged kernel, for A/B). ``test_hooks``: injectBitFlips=N (N bits spread over
+    the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
+    the device buffers between compute and check so tests can prove the checkers catch faults."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())))
     return _take(lib().mi355x_probe_run(dev, opts))
@@ -157,10 +163,32 @@ def sweep_release(dev: int) -> int:
     return int(lib().mi355x_probe_sweep_release(dev))
 
 
-def gemm_bf16(dev: int, a_ptr: int, bt_ptr: int, c_ptr: int, m: int, n: int, k: int) -> None:
-    """The probe's production MFMA GEMM on caller HOST buffers (C fp32 [m,n] = A bf16 [m,k] x
-    Bt bf16 [n,k]^T; e.g. CPU torch tensors' ``data_ptr()``), for independent numerics checks."""
-    rc = lib().mi355x_probe_gemm_bf16(dev, a_ptr, bt_ptr, c_ptr, m, n, k)
+_GEMM_OPTS = {"gemm_tile": "gemmTile", "gemm_pipe": "gemmPipe", "gemm_prio": "gemmPrio",
+              "gemm_vec_c": "gemmVecC", "gemm_group_m": "gemmGroupM", "poison_c": "poisonC"}
+
+
+def gemm_bf16(dev: int, a_ptr: int, bt_ptr: int, c_ptr: int, m: int, n: int, k: int,
+              **opts: int) -> None:
+    """One of the probe's MFMA GEMM kernels on caller HOST buffers (C fp32 [m,n] = A bf16 [m,k] x
+    Bt bf16 [n,k]^T; e.g. CPU torch tensors' ``data_ptr()``), for independent numerics checks.
+    Without options: the production kernel, as the claim-time probe launches it. Options (meanings
+    and defaults as for ``run``): ``gemm_tile`` 256 | 128, ``gemm_pipe`` 0 | 1 | 2 | 3 | 21 | 22,
+    ``gemm_prio``, ``gemm_vec_c``, ``gemm_group_m``, and ``poison_c`` (the device C starts as 0xFF
+    bytes, so an unwritten tile comes back as NaN). Tile 256 needs m, n % 256 == 0 and k % 64 == 0,
+    tile 128 m, n % 128 == 0 and k % 32 == 0; a timing-only pipe (11, 12) is refused."""
+    unknown = sorted(set(opts) - set(_GEMM_OPTS))
+    if unknown:
+        raise TypeError(f"gemm_bf16: unknown option(s) {unknown}")
+    if not opts:
+        rc = lib().mi355x_probe_gemm_bf16(dev, a_ptr, bt_ptr, c_ptr, m, n, k)
+    else:
+        if not hasattr(lib(), "mi355x_probe_gemm_bf16_opts"):
+            raise RuntimeError("libmi355x_probe.so predates the GEMM options: rebuild it")
+        js = json.dumps({_GEMM_OPTS[key]: int(v) for key, v in opts.items()}).encode()
+        rc = lib().mi355x_probe_gemm_bf16_opts(dev, a_ptr, bt_ptr, c_ptr, m, n, k, js)
+    if rc == -4:
+        raise RuntimeError("mi355x_probe_gemm_bf16 failed with a HIP error (rc=-4)")
     if rc != 0:
-        raise ValueError(f"mi355x_probe_gemm_bf16 failed (rc={rc}): m,n % 256 and k % 64 must be "
-                         f"0 and the device index valid")
+        raise ValueError(f"mi355x_probe_gemm_bf16 refused its arguments (rc={rc}): m, n must be "
+                         f"multiples of the tile (256 | 128), k of 64 | 32, the pipe one that "
+                         f"computes C and the device index valid")

@@ -25,7 +25,9 @@ char* mi355x_probe_identify(int device);
  *     "cus":{"expected","mfmaVerified","perXcd":[8],"gemmTiles","badWaves","ok"},"ms":...}
  * cus: every CU's matrix cores are exercised by a census kernel (chained MFMAs checked exactly per
  * wave, the CU identified by its XCC_ID/HW_ID registers); with requireAllCUs the probe fails
- * unless mfmaVerified >= the runtime's CU count. gemmTiles = CUs that ran tiles of the timed GEMM. */
+ * unless mfmaVerified >= the runtime's CU count. gemmTiles = CUs that ran tiles of the timed GEMM.
+ * Test hooks (corrupt a buffer between compute and check): "injectBitFlips":N flips N bits spread
+ * over the HBM region, "injectFlipAtChunk":i flips bit 0 of 16-byte chunk i, "injectGemmFault". */
 char* mi355x_probe_run(int device, const char* opts_json);
 /* xGMI peer check: src writes a pattern, copies it to dst over the peer link
  * (hipMemcpyPeerAsync after hipDeviceEnablePeerAccess), dst verifies every bit.
@@ -56,6 +58,14 @@ int mi355x_probe_sweep_release(int device);
  * 256, k of 64. For independent numerics checks against a CPU torch.matmul (torch bundles its own
  * HIP runtime, so device pointers cannot be shared with it in one process). 0 = ok. */
 int mi355x_probe_gemm_bf16(int device, const void* A, const void* Bt, void* C, int m, int n, int k);
+/* The same on any of the probe's GEMM kernels. opts (JSON or NULL), meanings and defaults as in
+ * mi355x_probe_run: "gemmTile" 256 | 128, "gemmPipe" 0 | 1 | 2 | 3 | 21 | 22 (256 only), "gemmPrio",
+ * "gemmVecC" (2-phase loop only), "gemmGroupM" (tile order), "poisonC" (the device C is filled with
+ * 0xFF bytes before the launch). Tile 256 needs m, n % 256 == 0 and k % 64 == 0; tile 128 m, n % 128
+ * == 0 and k % 32 == 0. 0 = ok, -1 bad device, -2 bad arguments (also: an unknown pipe or one of the
+ * timing-only ablations 11 / 12), -4 a HIP error. mi355x_probe_gemm_bf16 is this with NULL opts. */
+int mi355x_probe_gemm_bf16_opts(int device, const void* A, const void* Bt, void* C, int m, int n, int k,
+                                const char* opts_json);
 void mi355x_probe_free(char* p);
 
 #ifdef __cplusplus

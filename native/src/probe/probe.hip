@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "mi355x/probe.h"
+#include "tile_order.h"  // xcd_remap, grouped_tile
 
 #define PROBE_CHECK(expr)                                                                 \
   do {                                                                                    \
@@ -293,13 +294,6 @@ constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int LDS_STRIDE = BK + 8;  // +16 B pad per row: 80-B rows spread ds_read_b128 lane groups
 constexpr int kGemmThreads = 256;
 
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  // Bijective XCD-aware remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"):
-  // consecutive logical tiles land on the same XCD (shared L2) under round-robin dispatch.
-  int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-}
-
 __global__ __launch_bounds__(kGemmThreads, 2) void gemm_bf16_mfma_nt(const short* __restrict__ A,
                                                                       const short* __restrict__ Bt,
                                                                       float* __restrict__ C, int M,
@@ -440,20 +434,9 @@ __global__ __launch_bounds__(kGemm2Threads, 1) void gemm_bf16_mfma_256(const sho
   if (cu_map && threadIdx.x == 0) mark_cu(cu_map);  // which CUs ran GEMM tiles (probe report)
   const int tiles_n = N / G2_BN, tiles_m = M / G2_BM;
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  // Tile order inside each XCD's contiguous range of wg (xcd_remap): row-major (group_m <= 1) walks
-  // whole tile rows, so the tiles an XCD runs at once share one or two A panels but need a B panel
-  // each; grouped (group_m rows at a time, column-major inside a group) makes them a group_m x k
-  // block that shares both, less operand traffic into the XCD's 4 MB L2 per K-step. Bijective.
+  // tile order inside each XCD's contiguous range of wg: tile_order.h
   int tile_m, tile_n;
-  if (group_m > 1) {
-    const int per_group = group_m * tiles_n, first_m = (wg / per_group) * group_m;
-    const int gm = min(tiles_m - first_m, group_m), r = wg % per_group;
-    tile_m = first_m + r % gm;
-    tile_n = r / gm;
-  } else {
-    tile_m = wg / tiles_n;
-    tile_n = wg % tiles_n;
-  }
+  grouped_tile(wg, tiles_m, tiles_n, group_m, &tile_m, &tile_n);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
 
@@ -581,15 +564,7 @@ __global__ __launch_bounds__(kGemm2Threads, 1) void gemm_bf16_mfma_256p(const sh
   const int tiles_n = N / G2_BN, tiles_m = M / G2_BM;
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   int tile_m, tile_n;
-  if (group_m > 1) {
-    const int per_group = group_m * tiles_n, first_m = (wg / per_group) * group_m;
-    const int gm = min(tiles_m - first_m, group_m), r = wg % per_group;
-    tile_m = first_m + r % gm;
-    tile_n = r / gm;
-  } else {
-    tile_m = wg / tiles_n;
-    tile_n = wg % tiles_n;
-  }
+  grouped_tile(wg, tiles_m, tiles_n, group_m, &tile_m, &tile_n);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
 
@@ -786,15 +761,7 @@ __global__ __launch_bounds__(kGemm2Threads, 1) void gemm_bf16_mfma_256x(const sh
   const int tiles_n = N / G2_BN, tiles_m = M / G2_BM;
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   int tile_m, tile_n;
-  if (group_m > 1) {
-    const int per_group = group_m * tiles_n, first_m = (wg / per_group) * group_m;
-    const int gm = min(tiles_m - first_m, group_m), r = wg % per_group;
-    tile_m = first_m + r % gm;
-    tile_n = r / gm;
-  } else {
-    tile_m = wg / tiles_n;
-    tile_n = wg % tiles_n;
-  }
+  grouped_tile(wg, tiles_m, tiles_n, group_m, &tile_m, &tile_n);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
   const short* a_src[4];
@@ -1200,12 +1167,61 @@ std::string hip_uuid(int dev) {
   return "GPU-" + hex;
 }
 
+// Which GEMM kernel runs: the options "gemmTile", "gemmPipe", "gemmPrio", "gemmVecC" of a probe.
+struct GemmVariant {
+  int tile = 256;        // 128: the older 128x128 register-staged kernel
+  int pipe = kGemmPipe;  // K-loop of the 256x256 kernel (see kGemmPipe)
+  bool prio = false;     // 2-phase loop only
+  bool vec_c = false;    // 2-phase loop only
+};
+
+// A variant that computes C (not a timing-only ablation) and the shape its tile divides.
+bool gemm_args_ok(const GemmVariant& v, int m, int n, int k) {
+  if (v.tile != 256 && v.tile != 128) return false;
+  if (v.pipe != 0 && v.pipe != 1 && v.pipe != 2 && v.pipe != 3 && v.pipe != 21 && v.pipe != 22)
+    return false;
+  const int bm = v.tile == 256 ? G2_BM : BM, bn = v.tile == 256 ? G2_BN : BN, bk = v.tile == 256 ? G2_BK : BK;
+  return m > 0 && n > 0 && k > 0 && m % bm == 0 && n % bn == 0 && k % bk == 0;
+}
+
+// The one kernel dispatch: the probe's MFMA phase and the host-buffer entry points both launch
+// through it. Pipes 11 / 12 are the timing-only ablations (wrong C); any other unknown pipe runs
+// the 2-phase loop. The 128x128 kernel has no tile order option and marks no CUs.
+void launch_gemm(hipStream_t s, const GemmVariant& v, const short* A, const short* Bt, float* C, int M, int N, int K,
+                 unsigned long long* cu_map, int group_m) {
+  if (v.tile != 256) {
+    hipLaunchKernelGGL(gemm_bf16_mfma_nt, dim3((M / BM) * (N / BN)), dim3(kGemmThreads), 0, s, A, Bt, C, M, N, K);
+    return;
+  }
+  const dim3 grid((M / G2_BM) * (N / G2_BN)), block(kGemm2Threads);
+  if (v.pipe == 1)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<false>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 2)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 1>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 3)
+    hipLaunchKernelGGL(gemm_bf16_mfma_256x, grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 21)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 0>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 22)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 2>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 11)  // ablations (timing only; the checks fail)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 1, 1>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.pipe == 12)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 2, 1>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.prio)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256<true, false>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else if (v.vec_c)
+    hipLaunchKernelGGL((gemm_bf16_mfma_256<false, true>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+  else
+    hipLaunchKernelGGL((gemm_bf16_mfma_256<false, false>), grid, block, 0, s, A, Bt, C, M, N, K, cu_map, group_m);
+}
+
 // Enqueues the whole MFMA phase on stream s (no host sync): (a) a 256^3 GEMM checked element by
 // element against the VALU reference with asymmetric operands, (b) the timed N^3 GEMM (events
 // ctx.gev[0..1]) with exact u32 (mod 2^32) ABFT row/column checksums, then copies the two mismatch
 // counters to hres[kSlotSmall..kSlotAbft]. Operands are carved from ``gbase``. zero_mfma: the operand
 // kernels zero the phase's counters cnt[kSlotSmall..kResSlots) and ABFT accumulators themselves.
-void launch_mfma_phase(char* gbase, int gemm_n, bool tile256, int pipe, bool prio, bool vec_c, int group_m, int reps, int inject_gemm,
+void launch_mfma_phase(char* gbase, int gemm_n, const GemmVariant& variant, int group_m, int reps, int inject_gemm,
                        int census_fault_xcc, bool zero_mfma, bool poison_c, unsigned long long* cnt,
                        unsigned long long* hres, DeviceCtx& ctx, hipStream_t s) {
   const size_t n = static_cast<size_t>(gemm_n), n0 = 256;
@@ -1225,38 +1241,7 @@ void launch_mfma_phase(char* gbase, int gemm_n, bool tile256, int pipe, bool pri
   auto* c = reinterpret_cast<float*>(carve(n * n * 4));
   auto* v = reinterpret_cast<unsigned long long*>(carve(6 * n * 8));
   auto gemm = [&](const short* a_, const short* b_, float* c_, int nn, unsigned long long* cu_map) {
-    const dim3 grid((nn / G2_BM) * (nn / G2_BN));
-    if (tile256 && pipe == 1)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<false>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn, cu_map,
-                         group_m);
-    else if (tile256 && pipe == 2)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 1>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn, cu_map,
-                         group_m);
-    else if (tile256 && pipe == 3)
-      hipLaunchKernelGGL(gemm_bf16_mfma_256x, grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn, cu_map, group_m);
-    else if (tile256 && pipe == 21)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 0>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256 && pipe == 22)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 2>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256 && pipe == 11)  // ablations (timing only; the checks fail)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 1, 1>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256 && pipe == 12)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 2, 1>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256 && prio)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256<true, false>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256 && vec_c)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256<false, true>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else if (tile256)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256<false, false>), grid, dim3(kGemm2Threads), 0, s, a_, b_, c_, nn, nn, nn,
-                         cu_map, group_m);
-    else
-      hipLaunchKernelGGL(gemm_bf16_mfma_nt, dim3((nn / BM) * (nn / BN)), dim3(kGemmThreads), 0, s, a_, b_, c_, nn, nn, nn);
+    launch_gemm(s, variant, a_, b_, c_, nn, nn, nn, cu_map, group_m);
   };
   // (a) 256^3 full-element check vs the VALU reference; asymmetric operands
   const uint64_t e0 = static_cast<uint64_t>(n0) * n0;
@@ -1342,11 +1327,15 @@ std::string run_probe(int dev, const char* opts) {
   const int patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(opts, "patterns", 2))));
   const int inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(opts, "injectBitFlips", 0))));
   const int inject_gemm = static_cast<int>(opt_int(opts, "injectGemmFault", 0));
+  const long long inject_chunk = opt_int(opts, "injectFlipAtChunk", -1);  // test hook: one flip, bit 0 of a chunk
   const bool tile256 = opt_int(opts, "gemmTile", 256) != 128;  // 128 = the older 128x128 kernel (A/B)
   const int group_m = static_cast<int>(opt_int(opts, "gemmGroupM", kGemmGroupM));  // tile order (A/B)
   const int gemm_pipe = static_cast<int>(opt_int(opts, "gemmPipe", kGemmPipe));      // 1, 2: half-tile pipeline
-  const bool gemm_prio = opt_int(opts, "gemmPrio", 0) != 0;                        // s_setprio (A/B)
-  const bool gemm_vec_c = opt_int(opts, "gemmVecC", 0) != 0;                       // 16-B C stores (A/B)
+  GemmVariant variant;
+  variant.tile = tile256 ? 256 : 128;
+  variant.pipe = gemm_pipe;
+  variant.prio = opt_int(opts, "gemmPrio", 0) != 0;   // s_setprio (A/B)
+  variant.vec_c = opt_int(opts, "gemmVecC", 0) != 0;  // 16-B C stores (A/B)
   const bool poison_c = opt_int(opts, "poisonC", 0) != 0;                           // test hook
   // The HBM test is bandwidth-bound with few waves per CU; the MFMA phase is compute-bound and
   // touches ~130 MiB: run them concurrently on two streams (overlap=0: one stream, serial).
@@ -1445,7 +1434,7 @@ std::string run_probe(int dev, const char* opts) {
   // earlier on the GPU while the rest of the HBM test is still enqueued well ahead of need.
   const int hbm_first = static_cast<int>(opt_int(opts, "hbmFirst", 1));
   if (do_mfma && hbm_first == 0)
-    launch_mfma_phase(base + hbm_region, gemm_n, tile256, gemm_pipe, gemm_prio, gemm_vec_c, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
+    launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                       ctx, s2);
 
   // ---------------- HBM: all patterns back to back, per-pattern counters
@@ -1476,11 +1465,15 @@ std::string run_probe(int dev, const char* opts) {
       hipLaunchKernelGGL(hbm_fill<0>, dim3(fill_grid), dim3(kHbmThreads), 0, s, hbm, n16, seed, flip, reset, nreset);
     PROBE_CHECK(hipEventRecord(ctx.ev[1 + 2 * pi], s));
     if (pi == 0 && do_mfma && hbm_first == 2)
-      launch_mfma_phase(base + hbm_region, gemm_n, tile256, gemm_pipe, gemm_prio, gemm_vec_c, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
+      launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                         ctx, s2);
     if (pi == 0 && inject_flips > 0)
       hipLaunchKernelGGL(inject_bit_flips, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned int*>(hbm), n16 * 4,
                          inject_flips);
+    // inject_bit_flips on the words from chunk i on, with a stride of 0 words: flips bit 0 of p[0]
+    if (pi == 0 && inject_chunk >= 0 && static_cast<uint64_t>(inject_chunk) < n16)
+      hipLaunchKernelGGL(inject_bit_flips, dim3(1), dim3(256), 0, s,
+                         reinterpret_cast<unsigned int*>(hbm + static_cast<uint64_t>(inject_chunk)), uint64_t{0}, 1);
     if (tiled)
       hipLaunchKernelGGL((hbm_verify<1, 1>), dim3(verify_grid), dim3(kHbmThreads), 0, s, static_cast<const u32x4*>(hbm),
                          n16, seed, flip, cnt + 2 * pi, cnt + 2 * pi + 1);
@@ -1495,7 +1488,7 @@ std::string run_probe(int dev, const char* opts) {
   PROBE_CHECK(hipGetLastError());
   PROBE_CHECK(hipMemcpyAsync(hres, cnt, 2 * patterns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   if (do_mfma && hbm_first == 1)
-    launch_mfma_phase(base + hbm_region, gemm_n, tile256, gemm_pipe, gemm_prio, gemm_vec_c, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
+    launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                       ctx, s2);
   const double launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
   PROBE_CHECK(hipStreamSynchronize(s));
@@ -2125,9 +2118,17 @@ int mi355x_probe_sweep_release(int dev) {
   return 1;
 }
 
-int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int m, int n, int k) {
+int mi355x_probe_gemm_bf16_opts(int dev, const void* A, const void* Bt, void* C, int m, int n, int k,
+                                const char* opts_json) {
   if (g_count < 0 || dev < 0 || dev >= g_count) return -1;
-  if (m <= 0 || n <= 0 || k <= 0 || m % G2_BM || n % G2_BN || k % G2_BK || !A || !Bt || !C) return -2;
+  GemmVariant variant;
+  variant.tile = static_cast<int>(opt_int(opts_json, "gemmTile", 256));
+  variant.pipe = static_cast<int>(opt_int(opts_json, "gemmPipe", kGemmPipe));
+  variant.prio = opt_int(opts_json, "gemmPrio", 0) != 0;
+  variant.vec_c = opt_int(opts_json, "gemmVecC", 0) != 0;
+  const int group_m = static_cast<int>(opt_int(opts_json, "gemmGroupM", kGemmGroupM));
+  const bool poison_c = opt_int(opts_json, "poisonC", 0) != 0;
+  if (!A || !Bt || !C || !gemm_args_ok(variant, m, n, k)) return -2;
   std::lock_guard<std::mutex> g(device_mutex(dev));
   try {
     PROBE_CHECK(hipSetDevice(dev));
@@ -2139,19 +2140,10 @@ int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int 
     PROBE_CHECK(hipMalloc(&dc.p, sc));
     PROBE_CHECK(hipMemcpy(da.p, A, sa, hipMemcpyHostToDevice));
     PROBE_CHECK(hipMemcpy(db.p, Bt, sb, hipMemcpyHostToDevice));
-    const dim3 grid((m / G2_BM) * (n / G2_BN));
-    if (kGemmPipe == 2)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<true, 0, 1>), grid, dim3(kGemm2Threads), 0, nullptr,
-                         static_cast<const short*>(da.p), static_cast<const short*>(db.p), static_cast<float*>(dc.p), m,
-                         n, k, static_cast<unsigned long long*>(nullptr), kGemmGroupM);
-    else if (kGemmPipe == 1)
-      hipLaunchKernelGGL((gemm_bf16_mfma_256p<false>), grid, dim3(kGemm2Threads), 0, nullptr, static_cast<const short*>(da.p),
-                         static_cast<const short*>(db.p), static_cast<float*>(dc.p), m, n, k,
-                         static_cast<unsigned long long*>(nullptr), kGemmGroupM);
-    else
-      hipLaunchKernelGGL((gemm_bf16_mfma_256<false, false>), grid, dim3(kGemm2Threads), 0, nullptr,
-                         static_cast<const short*>(da.p), static_cast<const short*>(db.p), static_cast<float*>(dc.p), m,
-                         n, k, static_cast<unsigned long long*>(nullptr), kGemmGroupM);
+    // test hook: a tile the kernel never writes comes back as all-ones words (NaN)
+    if (poison_c) PROBE_CHECK(hipMemset(dc.p, 0xFF, sc));
+    launch_gemm(nullptr, variant, static_cast<const short*>(da.p), static_cast<const short*>(db.p),
+                static_cast<float*>(dc.p), m, n, k, nullptr, group_m);
     PROBE_CHECK(hipGetLastError());
     PROBE_CHECK(hipMemcpy(C, dc.p, sc, hipMemcpyDeviceToHost));
     return 0;
@@ -2159,6 +2151,10 @@ int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int 
     (void)hipGetLastError();
     return -4;
   }
+}
+
+int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int m, int n, int k) {
+  return mi355x_probe_gemm_bf16_opts(dev, A, Bt, C, m, n, k, nullptr);
 }
 
 void mi355x_probe_free(char* p) { std::free(p); }

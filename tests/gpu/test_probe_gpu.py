@@ -57,11 +57,17 @@ def test_probe_passes_and_is_fast(hip):
     assert best["mfma"]["tflops"] > 850, best["mfma"]
 
 
+def _first_flip_offset(nbytes: int, k: int) -> int:
+    """Byte offset of the lowest 16-byte chunk ``injectBitFlips=k`` corrupts: one bit in each of
+    the 32-bit words stride, 2 * stride, .. k * stride, stride = words // (k + 1)."""
+    return 16 * ((nbytes // 16 * 4 // (k + 1)) // 4)
+
+
 def test_hbm_checker_counts_injected_bit_flips(hip):
     r = hip.run(0, hbm_bytes=256 << 20, mfma=False, injectBitFlips=37)
     assert not r["passed"]
     assert r["hbm"]["badBits"] == 37  # every flipped bit found, nothing else
-    assert r["hbm"]["firstBadOffset"] is not None
+    assert r["hbm"]["firstBadOffset"] == _first_flip_offset(256 << 20, 37)
 
 
 def test_abft_detects_single_corrupted_element(hip):
@@ -182,10 +188,11 @@ def test_grouped_tile_order_is_exact(hip, n, group_m):
 
 @pytest.mark.parametrize("n", [256, 1280, 4096])
 def test_vectorised_c_store_gemm_is_exact(hip, n):
-    """The transposed-MFMA variant with 16-byte C stores (``gemmVecC``) computes the same C: the
+    """The transposed-MFMA variant with 16-byte C stores (``gemmVecC``, an option of the 2-phase
+    loop: ``gemmPipe`` 0) computes the same C: the
     256^3 element-by-element check against the VALU reference and the exact ABFT checksums pass,
     with C poisoned before the GEMM."""
-    r = hip.run(0, hbm_bytes=1 << 20, patterns=1, gemm_n=n, gemmVecC=1, poisonC=1)
+    r = hip.run(0, hbm_bytes=1 << 20, patterns=1, gemm_n=n, gemmPipe=0, gemmVecC=1, poisonC=1)
     assert r["passed"], r
     assert r["mfma"]["abftMismatches"] == 0 and r["mfma"]["elementMismatches"] == 0
 
@@ -226,7 +233,7 @@ def test_counters_reset_after_a_faulty_probe(hip, overlap, zero_in_kernel):
     kw = dict(hbm_bytes=256 << 20, gemm_n=1024, overlap=overlap, zeroInKernel=zero_in_kernel)
     bad = hip.run(0, injectBitFlips=7, injectGemmFault=1, injectCensusFaultXcc=3, **kw)
     assert not bad["passed"] and bad["hbm"]["badBits"] == 7 and bad["mfma"]["abftMismatches"] == 2
-    assert bad["hbm"]["firstBadOffset"] is not None and bad["cus"]["badWaves"] > 0
+    assert bad["hbm"]["firstBadOffset"] == _first_flip_offset(256 << 20, 7) and bad["cus"]["badWaves"] > 0
     clean = hip.run(0, **kw)
     assert clean["passed"], clean
     assert clean["hbm"]["badBits"] == 0 and clean["hbm"]["firstBadOffset"] is None
