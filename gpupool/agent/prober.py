@@ -234,6 +234,7 @@ class Prober:
         t0 = time.perf_counter()
         hbm = int(opts.get("hbmBytes", 1 << 30))
         mfma = bool(opts.get("mfma", True))
+        lowp = [str(d) for d in (opts.get("mfmaLowPrecision") or [])] if mfma else []
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -246,6 +247,8 @@ class Prober:
             args = {"hipUUID": dev.get("hipUUID", ""), "hbmBytes": hbm, "mfma": mfma,
                     "gemmN": self.gemm_n if floors else self.overlap_gemm_n,
                     "overlap": 0 if floors else 1, "hooks": self._hooks(dev)}
+            if lowp:
+                args["lowPrecision"] = lowp
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -258,10 +261,11 @@ class Prober:
             if self.mode == "inproc":
                 res = self._hip.run(ordinal, hbm_bytes=hbm, mfma=mfma,
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
-                                    overlap=0 if floors else 1)
+                                    overlap=0 if floors else 1, mfma_low_precision=tuple(lowp))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
-                       str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"])
+                       str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
+                    (["--low-precision", ",".join(lowp)] if lowp else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -302,7 +306,8 @@ class Prober:
 
     @staticmethod
     def explain(res: dict) -> dict:
-        """A failed probe names what failed (HBM bits, GEMM element/ABFT mismatches, CU census)."""
+        """A failed probe names what failed (HBM bits, GEMM element/ABFT mismatches, CU census;
+        for spec.probe.mfmaLowPrecision the dtype in brackets)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -317,6 +322,15 @@ class Prober:
             why.append(f"CUCensusFailed: {cus.get('mfmaVerified')}/{cus.get('expected')} CUs "
                        f"verified MFMA, per XCD {cus.get('perXcd')}, {cus.get('badWaves')} bad "
                        f"wave(s)")
+        for dtype, e in (res.get("lowp") or {}).items():
+            if e.get("ok", True):
+                continue
+            if e.get("elementMismatches") or e.get("abftMismatches"):
+                why.append(f"MFMAResultMismatch({dtype}): {e.get('elementMismatches', 0)} element / "
+                           f"{e.get('abftMismatches', 0)} ABFT mismatch(es)")
+            if e.get("badWaves") or e.get("cusVerified", 0) < cus.get("expected", 0):
+                why.append(f"CUCensusFailed({dtype}): {e.get('cusVerified')}/{cus.get('expected')} "
+                           f"CUs verified MFMA, {e.get('badWaves')} bad wave(s)")
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

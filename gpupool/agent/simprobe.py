@@ -14,6 +14,8 @@ SIM_HBM_GBPS = 4900.0
 SIM_MFMA_TFLOPS = 1200.0
 SIM_XGMI_GBPS = 64.0
 SIM_SWEEP_GBPS = 6000.0
+# the low-precision GEMMs at the claim-time size 2048^3 (profiles/lowp_gemm_rates.json)
+SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
 def fault(dev: dict, key: str):
@@ -39,6 +41,17 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                       "ok": dead == 0}
         if dead and not fail:
             res["passed"] = False
+        # spec.probe.mfmaLowPrecision: the same block the gfx950 probe reports; the overlay's
+        # ``lowpFault: "<dtype>"`` fails that dtype's ABFT check only
+        asked = list(opts.get("mfmaLowPrecision") or [])
+        if asked:
+            bad = fault(dev, "lowpFault")
+            res["lowp"] = {d: {"ok": d != bad, "n": 2048, "elementMismatches": 0,
+                               "abftMismatches": 2 if d == bad else 0,
+                               "tflops": SIM_LOWP_TFLOPS.get(d, 0.0), "ms": 0.05,
+                               "cusVerified": cus - dead, "badWaves": dead * 8} for d in asked}
+            if bad in asked:
+                res["passed"] = False
     if fail:
         res["error"] = "injected probe failure (fault overlay)"
     res["ms"] = (time.perf_counter() - t0) * 1e3

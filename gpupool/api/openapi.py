@@ -281,6 +281,15 @@ def _build(s: dict) -> Check:
                 for i, x in enumerate(v):
                     item_c(x, (trail, i), errs)
             checks.append(c_items)
+        if s.get("x-kubernetes-list-type") == "set":
+            def c_listset(v, trail, errs):
+                seen = set()
+                for i, x in enumerate(v):
+                    hk = repr(x)
+                    if hk in seen:
+                        errs.append(f"{_render((trail, i))}: Duplicate value: {x!r}")
+                    seen.add(hk)
+            checks.append(c_listset)
         if s.get("x-kubernetes-list-type") == "map":
             keys = list(s.get("x-kubernetes-list-map-keys", []))
 

@@ -37,6 +37,8 @@ ANN_POD_DEVICES = "gpupool.amd.com/devices"
 LABEL_GFX = "amd.com/gpu.family"
 LABEL_POOL = "gpupool.amd.com/pool"
 DEFAULT_RESOURCE = "amd.com/gpu"
+# spec.probe.mfmaLowPrecision items (gpupool/ops/lowp.py DTYPES, native/src/probe/lowp.h)
+LOW_PRECISION_DTYPES = ("fp8", "mxfp8", "mxfp4")
 
 # Mi355xJob: finalizer that deletes the job's pods before the job goes away, and the labels every
 # job pod carries (the controller lists pods by them and checks the owner UID).
@@ -170,6 +172,11 @@ DEVICE_STATUS = {
                 "xgmiGBps": {"type": "number"},
                 "cusVerified": _I32,
                 "cusExpected": _I32,
+                "lowPrecisionVerified": {
+                    "type": "array", "items": {"type": "string", "enum": list(LOW_PRECISION_DTYPES)},
+                    "description": "The spec.probe.mfmaLowPrecision dtypes whose census, "
+                                   "element-wise GEMM check and ABFT GEMM all passed on this GPU "
+                                   "(present only when the pool asks for any)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -234,6 +241,11 @@ MI355X_SPEC = {
                  "!has(self.autoscale.maxReplicas) || "
                  "self.autoscale.minReplicas <= self.autoscale.maxReplicas",
          "message": "autoscale.minReplicas must not exceed autoscale.maxReplicas"},
+        {"rule": "!has(self.probe) || !has(self.probe.mfmaLowPrecision) || "
+                 "size(self.probe.mfmaLowPrecision) == 0 || !has(self.probe.mfma) || "
+                 "self.probe.mfma",
+         "message": "probe.mfmaLowPrecision needs probe.mfma: the low-precision checks are part "
+                    "of the MFMA phase"},
     ],
     "properties": {
         "replicas": {**_I32, "minimum": 0, "maximum": 1024,
@@ -346,6 +358,18 @@ MI355X_SPEC = {
                 "hbmBytes": {**_I64, "minimum": 1 << 20, "maximum": 64 << 30,
                              "default": 1 << 30},
                 "mfma": {**_B, "default": True},
+                "mfmaLowPrecision": {
+                    "type": "array", "default": [], "maxItems": len(LOW_PRECISION_DTYPES),
+                    "x-kubernetes-list-type": "set",
+                    "items": {"type": "string", "enum": list(LOW_PRECISION_DTYPES)},
+                    "description": "Also prove the low-precision matrix cores at claim time and "
+                                   "on rechecks: fp8 (OCP e4m3fn on the unscaled fp8 MFMA), mxfp8 "
+                                   "(e4m3) and mxfp4 (e2m1) on the block-scaled MFMA with an E8M0 "
+                                   "scale per 32 K-elements. Each dtype adds a per-CU census on "
+                                   "its instruction, a small GEMM checked element by element "
+                                   "against a VALU reference and the probe GEMM with exact ABFT; "
+                                   "a failure fails DeviceProbePassed naming the dtype. The "
+                                   "bf16 check and minMfmaTflops are unchanged. Needs mfma."},
                 "minHbmGBps": {"type": "number", "minimum": 0, "default": 0,
                                "description": "Performance floor: a GPU whose probe measures "
                                               "less HBM write+read bandwidth (GB/s) fails "

@@ -11,7 +11,7 @@ import functools
 import json
 import threading
 
-from . import native_path
+from . import lowp, native_path
 
 _lib = None
 _lock = threading.Lock()
@@ -55,6 +55,10 @@ def lib() -> ctypes.CDLL:
                                                           ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                           ctypes.c_char_p]
+            if hasattr(l, "mi355x_probe_gemm_lowp"):  # absent from a library built before it
+                l.mi355x_probe_gemm_lowp.restype = ctypes.c_int
+                l.mi355x_probe_gemm_lowp.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
+                    [ctypes.c_int] * 3 + [ctypes.c_char_p]
             _lib = l
     return _lib
 
@@ -86,23 +90,31 @@ def identify(dev: int) -> dict:
 
 
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
-        patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, **test_hooks: int) -> dict:
+        patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
+        **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
-    older register-staged kernel, for A/B). ``test_hooks``: injectBitFlips=N (N bits spread over
+    older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
+    ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
+    gemm_n GEMM with ABFT on that dtype's matrix-core instruction, reported under "lowp" (needs
+    ``mfma``). ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
-                     int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())))
+                     int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())),
+                     tuple(mfma_low_precision))
     return _take(lib().mi355x_probe_run(dev, opts))
 
 
 @functools.lru_cache(maxsize=64)
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
-              gemm_tile: int, hooks: tuple) -> bytes:
+              gemm_tile: int, hooks: tuple, low_precision: tuple = ()) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
-    return json.dumps({"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
-                       "gemmReps": gemm_reps, "gemmTile": gemm_tile, **dict(hooks)}).encode()
+    opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
+            "gemmReps": gemm_reps, "gemmTile": gemm_tile, **dict(hooks)}
+    if low_precision:  # the library's option parser reads integers: a dtype bit mask
+        opts["mfmaLowPrecision"] = lowp.dtype_mask(low_precision)
+    return json.dumps(opts).encode()
 
 
 def peer(src: int, dst: int, nbytes: int = 64 << 20) -> dict:
@@ -192,3 +204,22 @@ def gemm_bf16(dev: int, a_ptr: int, bt_ptr: int, c_ptr: int, m: int, n: int, k: 
         raise ValueError(f"mi355x_probe_gemm_bf16 refused its arguments (rc={rc}): m, n must be "
                          f"multiples of the tile (256 | 128), k of 64 | 32, the pipe one that "
                          f"computes C and the device index valid")
+
+
+def gemm_lowp(dev: int, dtype: str, a_ptr: int, bt_ptr: int, scale_a_ptr: int | None,
+              scale_bt_ptr: int | None, c_ptr: int, m: int, n: int, k: int, poison_c: int = 0) -> None:
+    """The probe's low-precision MFMA GEMM on caller HOST buffers: C fp32 [m,n] = A [m,k] x Bt [n,k]^T
+    with ``dtype`` "fp8" | "mxfp8" (one e4m3 byte per element) | "mxfp4" (two e2m1 per byte, rows of
+    k/2 bytes); ``scale_*_ptr``: [rows][k/32] E8M0 bytes, None for "fp8". m, n, k multiples of 128.
+    Layouts and codecs: ``gpupool.ops.lowp``. A refused call (ValueError) leaves C untouched."""
+    if not hasattr(lib(), "mi355x_probe_gemm_lowp"):
+        raise RuntimeError("libmi355x_probe.so predates the low-precision GEMM: rebuild it")
+    js = json.dumps({"poisonC": int(poison_c)}).encode()
+    rc = lib().mi355x_probe_gemm_lowp(dev, lowp.dtype_index(dtype), a_ptr, bt_ptr, scale_a_ptr,
+                                      scale_bt_ptr, c_ptr, m, n, k, js)
+    if rc == -4:
+        raise RuntimeError("mi355x_probe_gemm_lowp failed with a HIP error (rc=-4)")
+    if rc != 0:
+        raise ValueError(f"mi355x_probe_gemm_lowp refused its arguments (rc={rc}): m, n, k must be "
+                         f"multiples of 128, scales given exactly for the scaled dtypes and the "
+                         f"device index valid")

@@ -61,6 +61,7 @@ struct Mi355xPoolSpec {
   bool probe_enabled = true;
   int64_t probe_hbm_bytes = 1LL << 30;
   bool probe_mfma = true;
+  std::vector<std::string> probe_mfma_low_precision;  // spec.probe.mfmaLowPrecision: fp8 | mxfp8 | mxfp4
   double probe_min_hbm_gbps = 0;     // performance floors (0 = off)
   double probe_min_mfma_tflops = 0;
   int64_t probe_recheck_seconds = 0;  // periodic re-probe of idle claimed GPUs (0 = off)

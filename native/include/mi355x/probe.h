@@ -27,7 +27,19 @@ char* mi355x_probe_identify(int device);
  * wave, the CU identified by its XCC_ID/HW_ID registers); with requireAllCUs the probe fails
  * unless mfmaVerified >= the runtime's CU count. gemmTiles = CUs that ran tiles of the timed GEMM.
  * Test hooks (corrupt a buffer between compute and check): "injectBitFlips":N flips N bits spread
- * over the HBM region, "injectFlipAtChunk":i flips bit 0 of 16-byte chunk i, "injectGemmFault". */
+ * over the HBM region, "injectFlipAtChunk":i flips bit 0 of 16-byte chunk i, "injectGemmFault".
+ *
+ * Low-precision matrix cores (opt-in): "mfmaLowPrecision":mask, bit 0 fp8 (OCP e4m3fn on
+ * v_mfma_f32_16x16x32_fp8_fp8), bit 1 mxfp8 (e4m3) and bit 2 mxfp4 (e2m1), both on
+ * v_mfma_scale_f32_16x16x128_f8f6f4 with an E8M0 scale per 32 K-elements. Ignored with "mfma":false.
+ * Each dtype adds, after the bf16 phase on its stream: a per-CU census on that instruction, a 256^3
+ * GEMM checked element by element against a VALU reference, and the gemmN GEMM with exact ABFT. The
+ * report then gains
+ *   "lowp":{"<dtype>":{"ok","n","elementMismatches","abftMismatches","tflops","ms","cusVerified",
+ *                      "badWaves"}}
+ * and "passed" also needs every entry's "ok". Without the option: no "lowp" key, no extra launch,
+ * the same arena. Test hooks: "injectLowpFault":mask (+1.0 at one element of those dtypes' C),
+ * "injectLowpCensusFaultXcc":x. */
 char* mi355x_probe_run(int device, const char* opts_json);
 /* xGMI peer check: src writes a pattern, copies it to dst over the peer link
  * (hipMemcpyPeerAsync after hipDeviceEnablePeerAccess), dst verifies every bit.
@@ -66,6 +78,14 @@ int mi355x_probe_gemm_bf16(int device, const void* A, const void* Bt, void* C, i
  * timing-only ablations 11 / 12), -4 a HIP error. mi355x_probe_gemm_bf16 is this with NULL opts. */
 int mi355x_probe_gemm_bf16_opts(int device, const void* A, const void* Bt, void* C, int m, int n, int k,
                                 const char* opts_json);
+/* The low-precision GEMM of the probe (128x128x128 tile) on caller HOST buffers: C[m][n] (fp32) =
+ * A[m][k] * Bt[n][k]^T. dtype 0 fp8, 1 mxfp8 (one e4m3 byte per element), 2 mxfp4 (two e2m1 per byte,
+ * even k in the low nibble: rows of k/2 bytes). scaleA / scaleBt: [rows][k/32] E8M0 bytes for the
+ * scaled dtypes, NULL for fp8. m, n, k multiples of 128. opts: "poisonC". 0 = ok, -1 bad device,
+ * -2 bad arguments (a bad shape, an unknown dtype, scales passed to fp8 or missing for a scaled
+ * dtype; C is not touched), -4 a HIP error. */
+int mi355x_probe_gemm_lowp(int device, int dtype, const void* A, const void* Bt, const void* scaleA,
+                           const void* scaleBt, void* C, int m, int n, int k, const char* opts_json);
 void mi355x_probe_free(char* p);
 
 #ifdef __cplusplus

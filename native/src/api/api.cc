@@ -79,6 +79,8 @@ Mi355xPoolSpec Mi355xPoolSpec::from(const Json& s) {
   p.probe_enabled = pr["enabled"].as_bool(true);
   p.probe_hbm_bytes = pr["hbmBytes"].as_int(1LL << 30);
   p.probe_mfma = pr["mfma"].as_bool(true);
+  for (const auto& d : pr["mfmaLowPrecision"].elements())
+    if (d.is_string()) p.probe_mfma_low_precision.push_back(d.as_string());
   p.probe_min_hbm_gbps = pr["minHbmGBps"].as_double(0);
   p.probe_min_mfma_tflops = pr["minMfmaTflops"].as_double(0);
   p.probe_recheck_seconds = pr["recheckSeconds"].as_int(0);
@@ -104,6 +106,11 @@ Json Mi355xPoolSpec::probe_json() const {
   j["enabled"] = probe_enabled;
   j["hbmBytes"] = probe_hbm_bytes;
   j["mfma"] = probe_mfma;
+  if (!probe_mfma_low_precision.empty()) {  // absent when unset: the default claim carries today's options
+    Json lp = Json::array();
+    for (const auto& d : probe_mfma_low_precision) lp.push_back(d);
+    j["mfmaLowPrecision"] = lp;
+  }
   j["minHbmGBps"] = probe_min_hbm_gbps;
   j["minMfmaTflops"] = probe_min_mfma_tflops;
   j["recheckSeconds"] = probe_recheck_seconds;
@@ -302,6 +309,25 @@ std::vector<std::string> validate_mi355x(const Json& obj) {
   if (pr.contains("hbmBytes")) {
     int64_t b = pr["hbmBytes"].as_int(0);
     if (b < (1LL << 20) || b > (64LL << 30)) errs.push_back("spec.probe.hbmBytes: must be within [1MiB, 64GiB]");
+  }
+  if (pr.contains("mfmaLowPrecision")) {
+    const Json& lp = pr["mfmaLowPrecision"];
+    if (!lp.is_array()) {
+      errs.push_back("spec.probe.mfmaLowPrecision: must be of type array");
+    } else {
+      std::vector<std::string> seen;
+      for (const auto& d : lp.elements()) {
+        const std::string v = d.is_string() ? d.as_string() : "";
+        if (!in(v, {"fp8", "mxfp8", "mxfp4"}))
+          errs.push_back("spec.probe.mfmaLowPrecision: Unsupported value");
+        else if (std::find(seen.begin(), seen.end(), v) != seen.end())
+          errs.push_back("spec.probe.mfmaLowPrecision: Duplicate value: " + v);
+        seen.push_back(v);
+      }
+      // the CRD's x-kubernetes-validations rule
+      if (lp.size() > 0 && pr.contains("mfma") && pr["mfma"].is_bool() && !pr["mfma"].as_bool(true))
+        errs.push_back("spec.probe: mfmaLowPrecision needs mfma");
+    }
   }
   if (pr.contains("recheckSeconds") && (!pr["recheckSeconds"].is_int() || pr["recheckSeconds"].as_int(0) < 0))
     errs.push_back("spec.probe.recheckSeconds: should be greater than or equal to 0");

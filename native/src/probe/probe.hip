@@ -1040,6 +1040,8 @@ __global__ void count_ne_u32(const uint32_t* __restrict__ a, const uint32_t* __r
   if ((threadIdx.x & 63) == 0 && d) atomicAdd(bad, static_cast<unsigned long long>(d));
 }
 
+#include "lowp.h"  // FP8 / MXFP8 / MXFP4 census, GEMM, reference and ABFT (opt-in "mfmaLowPrecision")
+
 // ------------------------------------------------------------------ host side
 constexpr long long kMaxPatterns = 4;
 // device counter / pinned host result slots: 2 per HBM pattern, then the two GEMM check counters
@@ -1071,6 +1073,9 @@ struct DeviceCtx {
   hipEvent_t gev[3] = {};         // GEMM timing + "counters zeroed" hand-off between the streams
   hipDeviceProp_t prop{};
   unsigned long long* host_res = nullptr;
+  // low-precision phase ("mfmaLowPrecision"): created by the first probe that asks for a dtype
+  hipEvent_t lev[lowp::kDtypes][2] = {};
+  unsigned long long* host_lowp = nullptr;
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;
@@ -1337,6 +1342,10 @@ std::string run_probe(int dev, const char* opts) {
   variant.prio = opt_int(opts, "gemmPrio", 0) != 0;   // s_setprio (A/B)
   variant.vec_c = opt_int(opts, "gemmVecC", 0) != 0;  // 16-B C stores (A/B)
   const bool poison_c = opt_int(opts, "poisonC", 0) != 0;                           // test hook
+  // bit d set: also check lowp::Dtype d (1 fp8, 2 mxfp8, 4 mxfp4); needs the MFMA phase
+  const int lowp_mask = do_mfma ? static_cast<int>(opt_int(opts, "mfmaLowPrecision", 0)) & ((1 << lowp::kDtypes) - 1) : 0;
+  const int inject_lowp = static_cast<int>(opt_int(opts, "injectLowpFault", 0));  // test hook: dtype mask
+  const int lowp_census_fault_xcc = static_cast<int>(opt_int(opts, "injectLowpCensusFaultXcc", -1));
   // The HBM test is bandwidth-bound with few waves per CU; the MFMA phase is compute-bound and
   // touches ~130 MiB: run them concurrently on two streams (overlap=0: one stream, serial).
   const bool overlap = opt_int(opts, "overlap", 1) != 0;
@@ -1353,6 +1362,12 @@ std::string run_probe(int dev, const char* opts) {
     PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx.host_res), kResSlots * sizeof(unsigned long long)));
     ctx.uuid = hip_uuid(dev);
     ctx.ready = true;
+  }
+  if (lowp_mask && !ctx.host_lowp) {
+    for (auto& pair : ctx.lev)
+      for (auto& e : pair) PROBE_CHECK(hipEventCreate(&e));
+    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ctx.host_lowp),
+                              lowp::kDtypes * lowp::kSlots * sizeof(unsigned long long)));
   }
   hipStream_t s = ctx.stream;
   const hipDeviceProp_t& prop = ctx.prop;
@@ -1373,7 +1388,12 @@ std::string run_probe(int dev, const char* opts) {
   const size_t gemm_bytes = do_mfma ? 2 * sz_a0 + 2 * sz_c0 + 2 * sz_a + sz_c + sz_v : 0;
   const size_t hbm_region = align(n16 * 16);
   const size_t region = hbm_region + gemm_bytes;
-  const size_t need = region + align(kResSlots * sizeof(unsigned long long));
+  // the low-precision phase's operand region and counters follow the probe's own counters, so a
+  // probe that asks for no dtype has the arena it always had
+  const size_t lowp_cnt_bytes = align(lowp::kDtypes * lowp::kSlots * sizeof(unsigned long long));
+  const size_t lowp_bytes = lowp_mask ? lowp_cnt_bytes + lowp::region_bytes(n) : 0;
+  const size_t lowp_off = region + align(kResSlots * sizeof(unsigned long long));
+  const size_t need = lowp_off + lowp_bytes;
   const bool keep = opt_int(opts, "keepArena", 1) != 0;
   if (ctx.arena && (ctx.arena_bytes < need || ctx.arena_bytes > 2 * need)) {
     (void)hipFree(ctx.arena);
@@ -1433,9 +1453,25 @@ std::string run_probe(int dev, const char* opts) {
   // hbmFirst=2: the MFMA phase is enqueued right after the first fill (in-process A/B), so it starts
   // earlier on the GPU while the rest of the HBM test is still enqueued well ahead of need.
   const int hbm_first = static_cast<int>(opt_int(opts, "hbmFirst", 1));
-  if (do_mfma && hbm_first == 0)
+  // The low-precision phase follows the bf16 MFMA phase on its stream: one dtype after the other
+  // through one shared operand / C region, their counters copied back together.
+  auto* lowp_cnt = reinterpret_cast<unsigned long long*>(base + lowp_off);
+  auto launch_lowp = [&]() {
+    if (!lowp_mask) return;
+    PROBE_CHECK(hipMemsetAsync(lowp_cnt, 0, lowp::kDtypes * lowp::kSlots * sizeof(unsigned long long), s2));
+    for (int d = 0; d < lowp::kDtypes; ++d)
+      if (lowp_mask >> d & 1)
+        lowp::launch_phase(s2, d, base + lowp_off + lowp_cnt_bytes, gemm_n, cus, lowp_cnt + d * lowp::kSlots, ctx.lev[d][0],
+                           ctx.lev[d][1], (inject_lowp >> d & 1) != 0, lowp_census_fault_xcc, poison_c);
+    PROBE_CHECK(hipGetLastError());
+    PROBE_CHECK(hipMemcpyAsync(ctx.host_lowp, lowp_cnt, lowp::kDtypes * lowp::kSlots * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, s2));
+  };
+  if (do_mfma && hbm_first == 0) {
     launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                       ctx, s2);
+    launch_lowp();
+  }
 
   // ---------------- HBM: all patterns back to back, per-pattern counters
   auto* hbm = reinterpret_cast<u32x4*>(base);
@@ -1464,9 +1500,11 @@ std::string run_probe(int dev, const char* opts) {
     else
       hipLaunchKernelGGL(hbm_fill<0>, dim3(fill_grid), dim3(kHbmThreads), 0, s, hbm, n16, seed, flip, reset, nreset);
     PROBE_CHECK(hipEventRecord(ctx.ev[1 + 2 * pi], s));
-    if (pi == 0 && do_mfma && hbm_first == 2)
+    if (pi == 0 && do_mfma && hbm_first == 2) {
       launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                         ctx, s2);
+      launch_lowp();
+    }
     if (pi == 0 && inject_flips > 0)
       hipLaunchKernelGGL(inject_bit_flips, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned int*>(hbm), n16 * 4,
                          inject_flips);
@@ -1487,9 +1525,11 @@ std::string run_probe(int dev, const char* opts) {
   }
   PROBE_CHECK(hipGetLastError());
   PROBE_CHECK(hipMemcpyAsync(hres, cnt, 2 * patterns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  if (do_mfma && hbm_first == 1)
+  if (do_mfma && hbm_first == 1) {
     launch_mfma_phase(base + hbm_region, gemm_n, variant, group_m, reps, inject_gemm, census_fault_xcc, zero_in_kernel, poison_c, cnt, hres,
                       ctx, s2);
+    launch_lowp();
+  }
   const double launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
   PROBE_CHECK(hipStreamSynchronize(s));
   const double hbm_wall_ms = ms_since(t_run);
@@ -1510,6 +1550,24 @@ std::string run_probe(int dev, const char* opts) {
     // every CU the runtime reports must have proven its matrix cores (requireAllCUs, default on)
     const bool cus_ok = !require_all_cus || census.total >= cus;
     mfma_ok = small_bad == 0 && abft_bad == 0 && census_bad == 0 && cus_ok;
+  }
+  // low-precision dtypes: each one's report entry; any failure fails the probe
+  bool lowp_ok = true;
+  std::string lowp_json;
+  for (int d = 0; d < lowp::kDtypes; ++d) {
+    if (!(lowp_mask >> d & 1)) continue;
+    const unsigned long long* r = ctx.host_lowp + d * lowp::kSlots;
+    float ms;
+    PROBE_CHECK(hipEventElapsedTime(&ms, ctx.lev[d][0], ctx.lev[d][1]));
+    const double tf = ms > 0 ? 2.0 * gemm_n * static_cast<double>(gemm_n) * gemm_n / (ms * 1e-3) / 1e12 : 0.0;
+    const int verified = count_cus(r + lowp::kSlotCensusMap).total;
+    const bool ok = r[lowp::kSlotSmall] == 0 && r[lowp::kSlotAbft] == 0 && r[lowp::kSlotCensusBad] == 0 &&
+                    (!require_all_cus || verified >= cus);
+    lowp_ok = lowp_ok && ok;
+    lowp_json += std::string(lowp_json.empty() ? "" : ",") + "\"" + lowp::kNames[d] + "\":{\"ok\":" + (ok ? "true" : "false") +
+                 ",\"n\":" + std::to_string(gemm_n) + ",\"elementMismatches\":" + std::to_string(r[lowp::kSlotSmall]) +
+                 ",\"abftMismatches\":" + std::to_string(r[lowp::kSlotAbft]) + ",\"tflops\":" + jnum(tf) + ",\"ms\":" + jnum(ms) +
+                 ",\"cusVerified\":" + std::to_string(verified) + ",\"badWaves\":" + std::to_string(r[lowp::kSlotCensusBad]) + "}";
   }
   const double mfma_wall_ms = do_mfma ? ms_since(t_run) : 0.0;
   unsigned long long bad_bits = 0, first_bad = ~0ull;
@@ -1541,7 +1599,7 @@ std::string run_probe(int dev, const char* opts) {
   out += "{\"device\":" + std::to_string(dev);
   out += ",\"hipUUID\":" + jstr(ctx.uuid);
   out += ",\"gcnArch\":" + jstr(prop.gcnArchName);
-  out += ",\"passed\":" + std::string(hbm_ok && mfma_ok ? "true" : "false");
+  out += ",\"passed\":" + std::string(hbm_ok && mfma_ok && lowp_ok ? "true" : "false");
   out += ",\"hbm\":{\"ok\":" + std::string(hbm_ok ? "true" : "false") + ",\"bytes\":" + std::to_string(n16 * 16) +
          ",\"patterns\":" + std::to_string(patterns) + ",\"badBits\":" + std::to_string(bad_bits) +
          ",\"firstBadOffset\":" + (first_bad == ~0ull ? std::string("null") : std::to_string(first_bad * 16)) +
@@ -1565,6 +1623,7 @@ std::string run_probe(int dev, const char* opts) {
     }
     out += "}";
   }
+  if (lowp_mask) out += ",\"lowp\":{" + lowp_json + "}";
   out += ",\"ms\":" + jnum(total_ms);
   out += ",\"phases\":{\"arenaReused\":" + std::string(reused ? "true" : "false") +
          ",\"setupMs\":" + jnum(setup_ms) + ",\"allocMs\":" + jnum(alloc_ms) + ",\"launchMs\":" + jnum(launch_ms) +
@@ -2144,6 +2203,42 @@ int mi355x_probe_gemm_bf16_opts(int dev, const void* A, const void* Bt, void* C,
     if (poison_c) PROBE_CHECK(hipMemset(dc.p, 0xFF, sc));
     launch_gemm(nullptr, variant, static_cast<const short*>(da.p), static_cast<const short*>(db.p),
                 static_cast<float*>(dc.p), m, n, k, nullptr, group_m);
+    PROBE_CHECK(hipGetLastError());
+    PROBE_CHECK(hipMemcpy(C, dc.p, sc, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (const std::exception&) {
+    (void)hipGetLastError();
+    return -4;
+  }
+}
+
+int mi355x_probe_gemm_lowp(int dev, int dtype, const void* A, const void* Bt, const void* scaleA, const void* scaleBt,
+                           void* C, int m, int n, int k, const char* opts_json) {
+  if (g_count < 0 || dev < 0 || dev >= g_count) return -1;
+  if (!A || !Bt || !C || !lowp::gemm_args_ok(dtype, m, n, k)) return -2;
+  if (lowp::scaled(dtype) ? (!scaleA || !scaleBt) : (scaleA || scaleBt)) return -2;
+  const bool poison_c = opt_int(opts_json, "poisonC", 0) != 0;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  try {
+    PROBE_CHECK(hipSetDevice(dev));
+    const size_t kb = static_cast<size_t>(k) * lowp::bits_of(dtype) / 8, ks = static_cast<size_t>(k) / 32;
+    const size_t sa = m * kb, sb = n * kb, sc = static_cast<size_t>(m) * n * 4;
+    DevBuf da, db, dsa, dsb, dc;
+    PROBE_CHECK(hipMalloc(&da.p, sa));
+    PROBE_CHECK(hipMalloc(&db.p, sb));
+    PROBE_CHECK(hipMalloc(&dc.p, sc));
+    PROBE_CHECK(hipMemcpy(da.p, A, sa, hipMemcpyHostToDevice));
+    PROBE_CHECK(hipMemcpy(db.p, Bt, sb, hipMemcpyHostToDevice));
+    if (lowp::scaled(dtype)) {
+      PROBE_CHECK(hipMalloc(&dsa.p, m * ks));
+      PROBE_CHECK(hipMalloc(&dsb.p, n * ks));
+      PROBE_CHECK(hipMemcpy(dsa.p, scaleA, m * ks, hipMemcpyHostToDevice));
+      PROBE_CHECK(hipMemcpy(dsb.p, scaleBt, n * ks, hipMemcpyHostToDevice));
+    }
+    if (poison_c) PROBE_CHECK(hipMemset(dc.p, 0xFF, sc));
+    lowp::launch_gemm(nullptr, dtype, static_cast<const uint8_t*>(da.p), static_cast<const uint8_t*>(db.p),
+                      static_cast<const uint8_t*>(dsa.p), static_cast<const uint8_t*>(dsb.p), static_cast<float*>(dc.p), m,
+                      n, k);
     PROBE_CHECK(hipGetLastError());
     PROBE_CHECK(hipMemcpy(C, dc.p, sc, hipMemcpyDeviceToHost));
     return 0;

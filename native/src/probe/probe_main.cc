@@ -1,7 +1,8 @@
 // mi355x-probe CLI: `mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma]
-// [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
+// [--low-precision fp8,mxfp8,mxfp4] [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
 // Equivalent of the reference's in-pod `nvidia-smi` smoke check (GPU调度平台搭建.md:134-138),
 // but it exercises HBM and the matrix cores instead of only enumerating the device.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@ int main(int argc, char** argv) {
   int gemm_n = 4096;
   bool mfma = true, all = true, list = false;
   int device = -1;
+  int lowp_mask = 0;  // "mfmaLowPrecision": bit 0 fp8, 1 mxfp8, 2 mxfp4
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -36,10 +38,24 @@ int main(int argc, char** argv) {
       gemm_n = std::atoi(next());
     } else if (a == "--no-mfma") {
       mfma = false;
+    } else if (a == "--low-precision") {
+      std::string v = next();
+      for (size_t p = 0; p <= v.size();) {
+        const size_t q = std::min(v.find(',', p), v.size());
+        const std::string d = v.substr(p, q - p);
+        if (d == "fp8") lowp_mask |= 1;
+        else if (d == "mxfp8") lowp_mask |= 2;
+        else if (d == "mxfp4") lowp_mask |= 4;
+        else {
+          std::fprintf(stderr, "unknown low-precision dtype '%s' (fp8, mxfp8, mxfp4)\n", d.c_str());
+          return 2;
+        }
+        p = q + 1;
+      }
     } else if (a == "--list") {
       list = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--list]\n");
+      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--low-precision fp8,mxfp8,mxfp4] [--list]\n");
       return 0;
     } else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -75,7 +91,11 @@ int main(int argc, char** argv) {
     return 0;
   }
   char opts[256];
-  std::snprintf(opts, sizeof opts, "{\"hbmBytes\":%lld,\"mfma\":%s,\"gemmN\":%d}", hbm, mfma ? "true" : "false", gemm_n);
+  if (lowp_mask)
+    std::snprintf(opts, sizeof opts, "{\"hbmBytes\":%lld,\"mfma\":%s,\"gemmN\":%d,\"mfmaLowPrecision\":%d}", hbm,
+                  mfma ? "true" : "false", gemm_n, lowp_mask);
+  else
+    std::snprintf(opts, sizeof opts, "{\"hbmBytes\":%lld,\"mfma\":%s,\"gemmN\":%d}", hbm, mfma ? "true" : "false", gemm_n);
   std::vector<std::string> results(devs.size());
   std::vector<std::thread> ths;
   for (size_t i = 0; i < devs.size(); ++i) {

@@ -87,6 +87,12 @@ Json DeviceView::status_json() const {
       p["cusVerified"] = probe.path("cus.mfmaVerified");
       p["cusExpected"] = probe.path("cus.expected");
     }
+    if (probe["lowp"].is_object()) {  // spec.probe.mfmaLowPrecision: the dtypes that passed on this GPU
+      Json verified = Json::array();
+      for (const auto& kv : probe["lowp"].members())
+        if (kv.second["ok"].as_bool(false)) verified.push_back(kv.first);
+      p["lowPrecisionVerified"] = verified;
+    }
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)

@@ -93,6 +93,10 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         "gemm-ab": [("gemm_kloop_ab", [PY, "scripts/gemm_kloop_ab.py"], 300, {})],
         "hbm-cache": [("hbm_cache_residency", [PY, "scripts/hbm_cache_residency.py"], 300, {})],
         "claim-gemm-ab": [("claim_probe_gemm_ab", [PY, "scripts/claim_probe_gemm_ab.py"], 300, {})],
+        # spec.probe.mfmaLowPrecision: rates beside bf16, cost in the claim probe (give
+        # lowp_claim_probe_cost.py --parent-lib DIR by hand for the default-path A/B)
+        "lowp": [("lowp_gemm_rates", [PY, "scripts/gemm_lowp_rates.py"], 300, {}),
+                 ("lowp_claim_probe_cost", [PY, "scripts/lowp_claim_probe_cost.py"], 600, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],
