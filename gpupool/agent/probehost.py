@@ -151,6 +151,7 @@ class _HipKernel:
             return hp.run(self.ordinal(a.get("hipUUID")), hbm_bytes=int(a["hbmBytes"]),
                           mfma=bool(a["mfma"]), gemm_n=int(a["gemmN"]), overlap=int(a["overlap"]),
                           mfma_low_precision=tuple(a.get("lowPrecision") or ()),
+                          host_link_bytes=int(a.get("hostLinkBytes") or 0),
                           **{k: int(v) for k, v in (a.get("testHooks") or {}).items()})
         if op == "sweep":
             return hp.hbm_sweep(self.ordinal(a.get("hipUUID")), int(a["offset"]), int(a["bytes"]),

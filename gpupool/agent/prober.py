@@ -30,6 +30,7 @@ import subprocess
 import threading
 import time
 
+from ..api import schema
 from ..ops import native_path
 from . import simprobe
 
@@ -235,13 +236,17 @@ class Prober:
         hbm = int(opts.get("hbmBytes", 1 << 30))
         mfma = bool(opts.get("mfma", True))
         lowp = [str(d) for d in (opts.get("mfmaLowPrecision") or [])] if mfma else []
+        # spec.probe.hostLinkCheck: bytes of pinned host memory tested over PCIe (0 = off)
+        hostlink = int(opts.get("hostLinkBytes") or schema.DEFAULT_HOST_LINK_BYTES) \
+            if opts.get("hostLinkCheck") else 0
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
             return simprobe.probe(dev, opts, self.sim_ms)
         # The HBM test and the MFMA phase normally overlap on two streams (~13 % shorter
         # probe). With performance floors the pool wants clean numbers: run them serially.
-        floors = float(opts.get("minHbmGBps") or 0) > 0 or float(opts.get("minMfmaTflops") or 0) > 0
+        floors = float(opts.get("minHbmGBps") or 0) > 0 or float(opts.get("minMfmaTflops") or 0) > 0 \
+            or (hostlink > 0 and float(opts.get("minHostLinkGBps") or 0) > 0)
         if self.mode in HELPER_MODES:
             timeout = float(opts.get("timeoutSeconds") or DEFAULT_TIMEOUT_S)
             args = {"hipUUID": dev.get("hipUUID", ""), "hbmBytes": hbm, "mfma": mfma,
@@ -249,6 +254,8 @@ class Prober:
                     "overlap": 0 if floors else 1, "hooks": self._hooks(dev)}
             if lowp:
                 args["lowPrecision"] = lowp
+            if hostlink:
+                args["hostLinkBytes"] = hostlink
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -261,11 +268,13 @@ class Prober:
             if self.mode == "inproc":
                 res = self._hip.run(ordinal, hbm_bytes=hbm, mfma=mfma,
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
-                                    overlap=0 if floors else 1, mfma_low_precision=tuple(lowp))
+                                    overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
+                                    host_link_bytes=hostlink)
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
-                    (["--low-precision", ",".join(lowp)] if lowp else [])
+                    (["--low-precision", ",".join(lowp)] if lowp else []) + \
+                    (["--host-link-bytes", str(hostlink)] if hostlink else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -281,13 +290,15 @@ class Prober:
 
     @staticmethod
     def apply_floors(res: dict, dev: dict, opts: dict) -> dict:
-        """Performance floors (spec.probe.minHbmGBps / minMfmaTflops): a GPU that computes
+        """Performance floors (spec.probe.minHbmGBps / minMfmaTflops / minHostLinkGBps, the last
+        on the slower direction of the PCIe host link): a GPU that computes
         correctly but slowly (throttled clocks, degraded HBM stack, bad cooling) fails the probe.
         Fault overlay ``probeScale`` (0..1) scales the measured numbers to exercise this path."""
         scale = (dev.get("faults") or {}).get("probeScale") or dev.get("probeScale")
         hbm, mfma = res.get("hbm") or {}, res.get("mfma") or {}
+        link = res.get("hostLink") or {}
         if scale:
-            for part, key in ((hbm, "GBps"), (mfma, "tflops")):
+            for part, key in ((hbm, "GBps"), (mfma, "tflops"), (link, "GBps")):
                 if isinstance(part.get(key), (int, float)):
                     part[key] = part[key] * float(scale)
         if not res.get("passed"):
@@ -299,6 +310,9 @@ class Prober:
         floor_m = float(opts.get("minMfmaTflops") or 0)
         if floor_m > 0 and mfma.get("enabled", True) and float(mfma.get("tflops") or 0) < floor_m:
             why.append(f"MFMA {float(mfma.get('tflops') or 0):.0f} TFLOP/s < floor {floor_m:.0f}")
+        floor_l = float(opts.get("minHostLinkGBps") or 0)
+        if floor_l > 0 and link and float(link.get("GBps") or 0) < floor_l:
+            why.append(f"host link {float(link.get('GBps') or 0):.1f} GB/s < floor {floor_l:.1f}")
         if why:
             res["passed"] = False
             res["error"] = "PerformanceBelowFloor: " + "; ".join(why)
@@ -307,7 +321,8 @@ class Prober:
     @staticmethod
     def explain(res: dict) -> dict:
         """A failed probe names what failed (HBM bits, GEMM element/ABFT mismatches, CU census;
-        for spec.probe.mfmaLowPrecision the dtype in brackets)."""
+        for spec.probe.mfmaLowPrecision the dtype in brackets; for spec.probe.hostLinkCheck the
+        bits flipped on the PCIe link and the host's sample of its own memory)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -331,6 +346,16 @@ class Prober:
             if e.get("badWaves") or e.get("cusVerified", 0) < cus.get("expected", 0):
                 why.append(f"CUCensusFailed({dtype}): {e.get('cusVerified')}/{cus.get('expected')} "
                            f"CUs verified MFMA, {e.get('badWaves')} bad wave(s)")
+        link = res.get("hostLink") or {}
+        if link and not link.get("ok", True):
+            parts = []
+            if link.get("badBits"):
+                parts.append(f"{link['badBits']} flipped bit(s), first at offset "
+                             f"{link.get('firstBadOffset')}")
+            if link.get("hostSampleMismatches"):
+                parts.append(f"{link['hostSampleMismatches']} of {link.get('hostSamples')} host "
+                             f"samples differ")
+            why.append("HostLinkMismatch: " + (", ".join(parts) or "check failed"))
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

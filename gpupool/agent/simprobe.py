@@ -9,12 +9,17 @@ from __future__ import annotations
 
 import time
 
+from ..api import schema
+
 # nominal numbers = the measured MI355X probe (profiles/r1c_probe_gemm_ab_real.json)
 SIM_HBM_GBPS = 4900.0
 SIM_MFMA_TFLOPS = 1200.0
 SIM_XGMI_GBPS = 64.0
 SIM_SWEEP_GBPS = 6000.0
 # the low-precision GEMMs at the claim-time size 2048^3 (profiles/lowp_gemm_rates.json)
+# the PCIe host link's slower direction (device -> host) at the default 4 MiB, alone on the GPU
+# (profiles/hostlink_rates.json)
+SIM_HOSTLINK_GBPS = 51.0
 SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
@@ -52,6 +57,20 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                                "cusVerified": cus - dead, "badWaves": dead * 8} for d in asked}
             if bad in asked:
                 res["passed"] = False
+    # spec.probe.hostLinkCheck: the block the gfx950 probe reports; the overlay's ``hostLinkFail``
+    # flips one bit on that GPU's link
+    if opts.get("hostLinkCheck"):
+        bad = bool(fault(dev, "hostLinkFail"))
+        nbytes = int(opts.get("hostLinkBytes") or schema.DEFAULT_HOST_LINK_BYTES)
+        res["hostLink"] = {"ok": not bad, "bytes": nbytes, "patterns": 2,
+                           "seed": 0x4C4B0000 + int(dev.get("index") or 0),
+                           "badBits": 1 if bad else 0, "firstBadOffset": 0 if bad else None,
+                           "hostSamples": 1026, "hostSampleMismatches": 0,
+                           "writeGBps": SIM_HOSTLINK_GBPS, "readGBps": SIM_HOSTLINK_GBPS,
+                           "GBps": SIM_HOSTLINK_GBPS, "ms": 4 * nbytes / (SIM_HOSTLINK_GBPS * 1e6),
+                           "allocMs": 0.0}
+        if bad:
+            res["passed"] = False
     if fail:
         res["error"] = "injected probe failure (fault overlay)"
     res["ms"] = (time.perf_counter() - t0) * 1e3

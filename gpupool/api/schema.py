@@ -39,6 +39,10 @@ LABEL_POOL = "gpupool.amd.com/pool"
 DEFAULT_RESOURCE = "amd.com/gpu"
 # spec.probe.mfmaLowPrecision items (gpupool/ops/lowp.py DTYPES, native/src/probe/lowp.h)
 LOW_PRECISION_DTYPES = ("fp8", "mxfp8", "mxfp4")
+# spec.probe.hostLinkBytes default: the largest power of two that adds no more than 0.24 ms to the
+# claim-time probe (4 MiB: +0.16 ms, 8 MiB: +0.37; no size >= 1 MiB hides entirely under the HBM
+# stream: profiles/hostlink_claim_probe_cost.json)
+DEFAULT_HOST_LINK_BYTES = 4 << 20
 
 # Mi355xJob: finalizer that deletes the job's pods before the job goes away, and the labels every
 # job pod carries (the controller lists pods by them and checks the owner UID).
@@ -177,6 +181,11 @@ DEVICE_STATUS = {
                     "description": "The spec.probe.mfmaLowPrecision dtypes whose census, "
                                    "element-wise GEMM check and ABFT GEMM all passed on this GPU "
                                    "(present only when the pool asks for any)."},
+                "hostLinkGBps": {
+                    "type": "number",
+                    "description": "The slower direction (GPU to host, host to GPU) of the "
+                                   "spec.probe.hostLinkCheck PCIe test in GB/s (present only "
+                                   "when the pool asks for the check)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -246,6 +255,11 @@ MI355X_SPEC = {
                  "self.probe.mfma",
          "message": "probe.mfmaLowPrecision needs probe.mfma: the low-precision checks are part "
                     "of the MFMA phase"},
+        {"rule": "!has(self.probe) || !has(self.probe.minHostLinkGBps) || "
+                 "self.probe.minHostLinkGBps <= 0 || "
+                 "has(self.probe.hostLinkCheck) && self.probe.hostLinkCheck",
+         "message": "probe.minHostLinkGBps needs probe.hostLinkCheck: the floor applies to the "
+                    "host-link check's measurement"},
     ],
     "properties": {
         "replicas": {**_I32, "minimum": 0, "maximum": 1024,
@@ -375,6 +389,33 @@ MI355X_SPEC = {
                                               "less HBM write+read bandwidth (GB/s) fails "
                                               "DeviceProbePassed (0 = off; MI355X measures "
                                               "~4900 with the default 1 GiB probe)."},
+                "hostLinkCheck": {**_B, "default": False,
+                                  "description": "Also test the PCIe link between the GPU and "
+                                                 "the host at claim time and on rechecks: the GPU "
+                                                 "writes an address-dependent pattern into pinned "
+                                                 "host memory over the link, reads it back and "
+                                                 "verifies every bit in both polarities, the host "
+                                                 "checks a sample of what reached its DRAM, and "
+                                                 "both directions are timed. A flipped bit fails "
+                                                 "DeviceProbePassed (HostLinkMismatch); the "
+                                                 "slower direction's GB/s is reported as "
+                                                 "status.devices[].probe.hostLinkGBps."},
+                "hostLinkBytes": {**_I64, "minimum": 1 << 20, "maximum": 1 << 30,
+                                  "default": DEFAULT_HOST_LINK_BYTES,
+                                  "description": "Bytes of pinned host memory the host-link "
+                                                 "check tests per pass (two passes, each "
+                                                 "written and read back). The default adds "
+                                                 "~0.16 ms to the 0.76 ms claim-time probe; "
+                                                 "16 MiB adds ~0.77 ms, 64 MiB ~4.2 ms."},
+                "minHostLinkGBps": {"type": "number", "minimum": 0, "default": 0,
+                                    "description": "Performance floor for the host-link check: "
+                                                   "a GPU whose slower link direction measures "
+                                                   "less (GB/s) fails DeviceProbePassed (0 = "
+                                                   "off; needs hostLinkCheck). A floor makes the "
+                                                   "probe serial, so the link is measured alone. "
+                                                   "MI355X on PCIe Gen5 x16 measures ~51 at "
+                                                   "the default 4 MiB, ~56 at 64 MiB, of the "
+                                                   "63 GB/s spec rate."},
                 "xgmiPeerCheck": {**_B, "default": True,
                                   "description": "For pools of 2+ GPUs: each GPU copies a "
                                                  "pattern to the next one over xGMI "

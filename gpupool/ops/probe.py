@@ -59,6 +59,12 @@ def lib() -> ctypes.CDLL:
                 l.mi355x_probe_gemm_lowp.restype = ctypes.c_int
                 l.mi355x_probe_gemm_lowp.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
                     [ctypes.c_int] * 3 + [ctypes.c_char_p]
+            if hasattr(l, "mi355x_probe_host_link"):  # absent from a library built before it
+                l.mi355x_probe_host_link.restype = ctypes.c_void_p
+                l.mi355x_probe_host_link.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p,
+                                                     ctypes.c_size_t]
+                l.mi355x_probe_host_link_geometry.restype = None
+                l.mi355x_probe_host_link_geometry.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
             _lib = l
     return _lib
 
@@ -91,30 +97,74 @@ def identify(dev: int) -> dict:
 
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
-        **test_hooks: int) -> dict:
+        host_link_bytes: int = 0, **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
     older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
     ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
     gemm_n GEMM with ABFT on that dtype's matrix-core instruction, reported under "lowp" (needs
-    ``mfma``). ``test_hooks``: injectBitFlips=N (N bits spread over
+    ``mfma``). ``host_link_bytes`` > 0 adds the PCIe host-link phase over that many bytes of pinned
+    host memory (written and read back by the GPU over the link, every bit verified, both
+    directions timed), reported under "hostLink". ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())),
-                     tuple(mfma_low_precision))
+                     tuple(mfma_low_precision), int(host_link_bytes))
     return _take(lib().mi355x_probe_run(dev, opts))
 
 
 @functools.lru_cache(maxsize=64)
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
-              gemm_tile: int, hooks: tuple, low_precision: tuple = ()) -> bytes:
+              gemm_tile: int, hooks: tuple, low_precision: tuple = (),
+              host_link_bytes: int = 0) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
     opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
             "gemmReps": gemm_reps, "gemmTile": gemm_tile, **dict(hooks)}
     if low_precision:  # the library's option parser reads integers: a dtype bit mask
         opts["mfmaLowPrecision"] = lowp.dtype_mask(low_precision)
+    if host_link_bytes > 0:  # absent when off: the default options stay what they were
+        opts["hostLinkBytes"] = host_link_bytes
     return json.dumps(opts).encode()
+
+
+def host_link_geometry() -> dict:
+    """The default launch shape of the host-link kernels {"grid", "threads", "unroll"}: one pass of
+    the main loop of the whole grid covers grid * threads * unroll 16-byte chunks."""
+    if not hasattr(lib(), "mi355x_probe_host_link"):
+        raise RuntimeError("libmi355x_probe.so predates the host-link check: rebuild it")
+    g, t, u = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib().mi355x_probe_host_link_geometry(ctypes.byref(g), ctypes.byref(t), ctypes.byref(u))
+    return {"grid": g.value, "threads": t.value, "unroll": u.value}
+
+
+def host_link(dev: int, nbytes: int, patterns: int = 2, preload=None, want_bytes: int = 0,
+              **hooks: int) -> dict:
+    """The host-link phase alone (``mi355x_probe_host_link``): ``nbytes // 16`` chunks of pinned
+    host memory written by the GPU over PCIe, read back and verified, ``patterns`` passes. ->
+    the "hostLink" block of ``run`` plus "device" and "passed". ``want_bytes`` > 0: the first
+    ``min(want_bytes, tested bytes)`` of the pinned buffer after the run come back under "data"
+    (bytes). ``preload`` (a bytes-like object or a C-contiguous uint8 numpy array): no write pass;
+    the buffer is loaded from it and verified once against polarity 0 over ``len(preload) // 16``
+    chunks (``nbytes`` is ignored). ``hooks``: injectHostLinkFlipAtChunk=i and the sweep's knobs
+    hostLinkGrid / hostLinkUnroll / hostLinkNT / hostLinkCoherent."""
+    if not hasattr(lib(), "mi355x_probe_host_link"):
+        raise RuntimeError("libmi355x_probe.so predates the host-link check: rebuild it")
+    opts = {"hostLinkBytes": int(nbytes), "hostLinkPatterns": int(patterns),
+            **{k: int(v) for k, v in hooks.items()}}
+    buf, n = None, 0
+    if preload is not None:
+        raw = bytes(preload) if not hasattr(preload, "tobytes") else preload.tobytes()
+        n = len(raw)
+        buf = ctypes.create_string_buffer(raw, n)
+        opts["preload"] = 1
+    elif want_bytes > 0:
+        n = int(want_bytes)
+        buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_host_link(dev, json.dumps(opts).encode(), buf, n))
+    if buf is not None and want_bytes > 0 and "bytes" in res:
+        res["data"] = buf.raw[:min(int(want_bytes), n, int(res["bytes"]))]
+    return res
 
 
 def peer(src: int, dst: int, nbytes: int = 64 << 20) -> dict:

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "gpupool/generated/schema_consts.h"
 #include "gpupool/json.h"
 
 namespace gpupool {
@@ -62,6 +63,9 @@ struct Mi355xPoolSpec {
   int64_t probe_hbm_bytes = 1LL << 30;
   bool probe_mfma = true;
   std::vector<std::string> probe_mfma_low_precision;  // spec.probe.mfmaLowPrecision: fp8 | mxfp8 | mxfp4
+  bool probe_host_link_check = false;  // spec.probe.hostLinkCheck: PCIe host-link test (opt-in)
+  int64_t probe_host_link_bytes = gen::kDefaultProbeHostLinkBytes;
+  double probe_min_host_link_gbps = 0;
   double probe_min_hbm_gbps = 0;     // performance floors (0 = off)
   double probe_min_mfma_tflops = 0;
   int64_t probe_recheck_seconds = 0;  // periodic re-probe of idle claimed GPUs (0 = off)

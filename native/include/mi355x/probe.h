@@ -39,8 +39,40 @@ char* mi355x_probe_identify(int device);
  *                      "badWaves"}}
  * and "passed" also needs every entry's "ok". Without the option: no "lowp" key, no extra launch,
  * the same arena. Test hooks: "injectLowpFault":mask (+1.0 at one element of those dtypes' C),
- * "injectLowpCensusFaultXcc":x. */
+ * "injectLowpCensusFaultXcc":x.
+ *
+ * Host link (opt-in): "hostLinkBytes":N (0 / absent: off) tests N / 16 chunks of a pinned, device-mapped
+ * host buffer over PCIe: per pass the GPU writes the HBM test's address-dependent pattern into host
+ * memory (device -> host), reads it back (host -> device) and verifies every bit; "hostLinkPatterns"
+ * passes (default 2, 1..4), odd passes in the complementary polarity, seed 0x4C4B0000 + device. After
+ * the final synchronise the host recomputes the last pass's pattern at 1024 evenly spaced chunks plus
+ * the first and the last and compares them with its DRAM. With "overlap" the phase runs on a stream of
+ * its own beside the HBM and MFMA phases; with "overlap":0 last on the one stream, alone on the GPU.
+ * The report then gains
+ *   "hostLink":{"ok","bytes","patterns","seed","badBits","firstBadOffset","hostSamples",
+ *               "hostSampleMismatches","writeGBps","readGBps","GBps","ms","allocMs"}
+ * writeGBps device -> host, readGBps host -> device, GBps the slower of the two; allocMs the pinned
+ * allocation's cost when this probe made or grew it, else 0; ok = no bad bit and no sample mismatch,
+ * and "passed" also needs it. The buffer, the stream and the events are made by the first probe that
+ * asks, the buffer grown when a larger size is asked for, never shrunk and never trimmed. Without the
+ * option: no "hostLink" key, no extra launch, allocation, stream or event. Test hook:
+ * "injectHostLinkFlipAtChunk":i — once the first write pass has completed (the one case with a
+ * stream synchronise inside the phase) the HOST flips bit 0 of chunk i; out of range: no flip.
+ * A/B knobs of the measurement sweep: "hostLinkGrid", "hostLinkUnroll" (4 | 8 | 16), "hostLinkNT",
+ * "hostLinkCoherent", "hostLinkStream" (1: the tail of the MFMA stream). */
 char* mi355x_probe_run(int device, const char* opts_json);
+/* The host-link phase alone, on the device's first stream, under the device's probe lock; the
+ * "hostLink" block (after "device" and "passed") is the whole report. opts as above ("hostLinkBytes",
+ * "hostLinkPatterns", the hook, the knobs). io may be NULL; after the run the first min(io_bytes, bytes)
+ * of the pinned buffer are copied into it. "preload":1 skips the write passes: the first io_bytes of the
+ * pinned buffer are loaded from io and one verify of polarity 0 runs over io_bytes / 16 chunks — a pure
+ * host -> device check of data the caller made (no host sample, writeGBps 0, GBps = readGBps). A bad
+ * device, preload without io, or a size outside [16 B, 4 GiB]: {"passed":false,"error":...}. */
+char* mi355x_probe_host_link(int device, const char* opts_json, void* io, size_t io_bytes);
+/* The default launch shape of the host-link kernels: workgroups, threads per workgroup, 16-byte
+ * accesses per thread and main-loop iteration. One main-loop pass of the whole grid covers
+ * grid * threads * unroll chunks. Any pointer may be NULL. */
+void mi355x_probe_host_link_geometry(int* grid, int* threads, int* unroll);
 /* xGMI peer check: src writes a pattern, copies it to dst over the peer link
  * (hipMemcpyPeerAsync after hipDeviceEnablePeerAccess), dst verifies every bit.
  * opts: {"bytes":268435456}. src == dst runs the same path as a local device copy.

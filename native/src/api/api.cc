@@ -81,6 +81,9 @@ Mi355xPoolSpec Mi355xPoolSpec::from(const Json& s) {
   p.probe_mfma = pr["mfma"].as_bool(true);
   for (const auto& d : pr["mfmaLowPrecision"].elements())
     if (d.is_string()) p.probe_mfma_low_precision.push_back(d.as_string());
+  p.probe_host_link_check = pr["hostLinkCheck"].as_bool(false);
+  p.probe_host_link_bytes = pr["hostLinkBytes"].as_int(gen::kDefaultProbeHostLinkBytes);
+  p.probe_min_host_link_gbps = pr["minHostLinkGBps"].as_double(0);
   p.probe_min_hbm_gbps = pr["minHbmGBps"].as_double(0);
   p.probe_min_mfma_tflops = pr["minMfmaTflops"].as_double(0);
   p.probe_recheck_seconds = pr["recheckSeconds"].as_int(0);
@@ -110,6 +113,11 @@ Json Mi355xPoolSpec::probe_json() const {
     Json lp = Json::array();
     for (const auto& d : probe_mfma_low_precision) lp.push_back(d);
     j["mfmaLowPrecision"] = lp;
+  }
+  if (probe_host_link_check) {  // absent when off: the default claim carries today's options
+    j["hostLinkCheck"] = true;
+    j["hostLinkBytes"] = probe_host_link_bytes;
+    j["minHostLinkGBps"] = probe_min_host_link_gbps;
   }
   j["minHbmGBps"] = probe_min_hbm_gbps;
   j["minMfmaTflops"] = probe_min_mfma_tflops;
@@ -337,9 +345,19 @@ std::vector<std::string> validate_mi355x(const Json& obj) {
       (!pr["timeoutSeconds"].is_number() || pr["timeoutSeconds"].as_double(0) < 0.1 ||
        pr["timeoutSeconds"].as_double(0) > 600))
     errs.push_back("spec.probe.timeoutSeconds: must be within [0.1, 600]");
-  for (const char* k : {"minHbmGBps", "minMfmaTflops", "minXgmiGBps"})
+  for (const char* k : {"minHbmGBps", "minMfmaTflops", "minXgmiGBps", "minHostLinkGBps"})
     if (pr.contains(k) && (!pr[k].is_number() || pr[k].as_double(0) < 0))
       errs.push_back(std::string("spec.probe.") + k + ": should be greater than or equal to 0");
+  if (pr.contains("hostLinkCheck") && !pr["hostLinkCheck"].is_bool())
+    errs.push_back("spec.probe.hostLinkCheck: must be of type boolean");
+  if (pr.contains("hostLinkBytes")) {
+    const int64_t b = pr["hostLinkBytes"].is_int() ? pr["hostLinkBytes"].as_int(0) : 0;
+    if (b < (1LL << 20) || b > (1LL << 30)) errs.push_back("spec.probe.hostLinkBytes: must be within [1MiB, 1GiB]");
+  }
+  // the CRD's x-kubernetes-validations rule
+  if (pr["minHostLinkGBps"].is_number() && pr["minHostLinkGBps"].as_double(0) > 0 &&
+      !(pr["hostLinkCheck"].is_bool() && pr["hostLinkCheck"].as_bool(false)))
+    errs.push_back("spec.probe: minHostLinkGBps needs hostLinkCheck");
   const Json& part = s["partition"];
   if (part.contains("compute") && !in(part["compute"].as_string(), {"Any", "SPX", "DPX", "QPX", "CPX"}))
     errs.push_back("spec.partition.compute: Unsupported value");

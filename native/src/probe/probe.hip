@@ -58,7 +58,7 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // ------------------------------------------------------------------ HBM pattern test
-__device__ __forceinline__ uint32_t pattern_word(uint64_t idx, uint32_t seed) {
+__host__ __device__ __forceinline__ uint32_t pattern_word(uint64_t idx, uint32_t seed) {
   // Cheap invertible mix of the word index: distinct per address, dense in both bit values.
   uint32_t x = static_cast<uint32_t>(idx) * 0x9E3779B1u ^ static_cast<uint32_t>(idx >> 32) * 0x85EBCA77u;
   x ^= seed;
@@ -73,8 +73,9 @@ __device__ __forceinline__ uint32_t pattern_word(uint64_t idx, uint32_t seed) {
 // a bijective mix of the chunk index, its 4 words byte rotations of it XOR fixed masks. Both keep
 // every chunk distinct from every other (an aliased address line reads another chunk's pattern)
 // and both bit values dense; the complementary pass (flip) drives every bit to 0 and 1 either way.
+// __host__ too: the host-link phase recomputes a sample of the pattern on the CPU (hostlink.h).
 template <int kPat>
-__device__ __forceinline__ u32x4 pattern16(uint64_t i16, uint32_t seed, uint32_t flip) {
+__host__ __device__ __forceinline__ u32x4 pattern16(uint64_t i16, uint32_t seed, uint32_t flip) {
   u32x4 v;
   if constexpr (kPat == 0) {
     uint64_t w = i16 * 4;
@@ -1040,6 +1041,7 @@ __global__ void count_ne_u32(const uint32_t* __restrict__ a, const uint32_t* __r
   if ((threadIdx.x & 63) == 0 && d) atomicAdd(bad, static_cast<unsigned long long>(d));
 }
 
+#include "hostlink.h"  // PCIe host-link write / verify kernels (opt-in "hostLinkBytes")
 #include "lowp.h"  // FP8 / MXFP8 / MXFP4 census, GEMM, reference and ABFT (opt-in "mfmaLowPrecision")
 
 // ------------------------------------------------------------------ host side
@@ -1076,6 +1078,18 @@ struct DeviceCtx {
   // low-precision phase ("mfmaLowPrecision"): created by the first probe that asks for a dtype
   hipEvent_t lev[lowp::kDtypes][2] = {};
   unsigned long long* host_lowp = nullptr;
+  // host-link phase ("hostLinkBytes"): created by the first probe that asks. The pinned buffer is
+  // grown when a larger size is asked for, never shrunk, kept for the life of the process (trim
+  // leaves it: it is host RAM, not VRAM) and only ever freed or replaced by ensure_host_link, under
+  // the device's probe lock and after every stream that can use it has been synchronised.
+  hipStream_t hl_stream = nullptr;  // only with "overlap"
+  hipEvent_t hev[1 + 2 * kMaxPatterns] = {};
+  void* hl_buf = nullptr;  // host address
+  void* hl_dev = nullptr;  // the same memory as the GPU addresses it
+  uint64_t hl_bytes = 0;
+  bool hl_coherent = true;
+  unsigned long long* hl_cnt = nullptr;  // device counter pairs, one per pass
+  unsigned long long* hl_res = nullptr;  // their pinned copy
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;
@@ -1324,6 +1338,135 @@ CuCount count_cus(const unsigned long long* map) {
   return c;
 }
 
+// ------------------------------------------------------------------ host-link phase (hostlink.h)
+constexpr uint64_t kHostLinkMaxBytes = 4ull << 30;
+constexpr int kHostLinkSamples = 1024;
+
+// The options of the phase; n16 == 0: not asked for. ``bytes``: "hostLinkBytes", or the caller's
+// buffer for a preload.
+hostlink::Plan host_link_plan(int dev, const char* opts, uint64_t bytes) {
+  hostlink::Plan pl;
+  pl.n16 = bytes / 16;
+  pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(opts, "hostLinkPatterns", 2))));
+  pl.seed = 0x4C4B0000u + static_cast<uint32_t>(dev);
+  pl.inject_chunk = opt_int(opts, "injectHostLinkFlipAtChunk", -1);
+  pl.grid = static_cast<int>(std::min<long long>(hostlink::kMaxGrid, std::max(1LL, opt_int(opts, "hostLinkGrid", hostlink::kGrid))));
+  pl.unroll = static_cast<int>(opt_int(opts, "hostLinkUnroll", hostlink::kUnroll));
+  pl.nt = opt_int(opts, "hostLinkNT", hostlink::kNonTemporal) != 0;
+  pl.coherent = opt_int(opts, "hostLinkCoherent", hostlink::kCoherent) != 0;
+  return pl;
+}
+
+// Makes the phase's events, counters and a pinned, device-mapped buffer of at least ``bytes``.
+// The only place the buffer is freed or replaced: the caller holds the device's probe lock, and
+// every stream a kernel with the old pointer could be on is drained first. Returns the cost of the
+// pinned allocation when this call made or grew it, else 0.
+double ensure_host_link(DeviceCtx& c, uint64_t bytes, bool coherent) {
+  if (!c.hl_res) {  // set last: a failure half way is picked up by the next probe that asks
+    for (auto& e : c.hev)
+      if (!e) PROBE_CHECK(hipEventCreate(&e));
+    if (!c.hl_cnt)
+      PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.hl_cnt), 2 * kMaxPatterns * sizeof(unsigned long long)));
+    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.hl_res), 2 * kMaxPatterns * sizeof(unsigned long long)));
+  }
+  if (c.hl_buf && c.hl_bytes >= bytes && c.hl_coherent == coherent) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (c.hl_buf) {
+    if (c.hl_stream) PROBE_CHECK(hipStreamSynchronize(c.hl_stream));
+    PROBE_CHECK(hipStreamSynchronize(c.stream));
+    PROBE_CHECK(hipStreamSynchronize(c.stream2));
+    void* old = c.hl_buf;
+    c.hl_buf = c.hl_dev = nullptr;
+    c.hl_bytes = 0;
+    PROBE_CHECK(hipHostFree(old));
+  }
+  void* host = nullptr;
+  void* devp = nullptr;
+  const uint64_t cap = (bytes + 4095) & ~4095ull;
+  PROBE_CHECK(hipHostMalloc(&host, cap, hipHostMallocMapped | (coherent ? hipHostMallocCoherent : hipHostMallocNonCoherent)));
+  if (hipHostGetDevicePointer(&devp, host, 0) != hipSuccess || !devp) {
+    (void)hipHostFree(host);
+    throw ProbeError("hipHostGetDevicePointer failed for the host-link buffer");
+  }
+  c.hl_buf = host;
+  c.hl_dev = devp;
+  c.hl_bytes = cap;
+  c.hl_coherent = coherent;
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Enqueues the phase on stream s: per pass a write (device -> host), an event, a verify (host ->
+// device), an event; then the counters' copy. No host synchronise, except for the flip hook.
+void launch_host_link(DeviceCtx& c, hipStream_t s, const hostlink::Plan& pl) {
+  auto* buf = static_cast<u32x4*>(c.hl_dev);
+  PROBE_CHECK(hipEventRecord(c.hev[0], s));
+  for (int pi = 0; pi < pl.patterns; ++pi) {
+    const uint32_t flip = (pi & 1) ? 0xFFFFFFFFu : 0u;  // complementary polarity on odd passes
+    unsigned long long* reset = pi == 0 ? c.hl_cnt : nullptr;
+    // a preload keeps the caller's data: the write kernel only resets the counters (n16 = 0)
+    hostlink::launch_write(s, pl, buf, pl.preload ? 0 : pl.n16, flip, reset, reset ? pl.patterns : 0);
+    PROBE_CHECK(hipEventRecord(c.hev[1 + 2 * pi], s));
+    if (pi == 0 && pl.inject_chunk >= 0 && static_cast<uint64_t>(pl.inject_chunk) < pl.n16) {
+      // test hook: the HOST flips bit 0 of a chunk once the write pass has landed
+      PROBE_CHECK(hipStreamSynchronize(s));
+      static_cast<volatile uint32_t*>(c.hl_buf)[static_cast<uint64_t>(pl.inject_chunk) * 4] ^= 1u;
+      std::atomic_thread_fence(std::memory_order_seq_cst);
+    }
+    hostlink::launch_verify(s, pl, buf, flip, c.hl_cnt + 2 * pi, c.hl_cnt + 2 * pi + 1);
+    PROBE_CHECK(hipEventRecord(c.hev[2 + 2 * pi], s));
+  }
+  PROBE_CHECK(hipGetLastError());
+  PROBE_CHECK(hipMemcpyAsync(c.hl_res, c.hl_cnt, 2 * pl.patterns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+}
+
+// After the stream's synchronise: timings, counters, the host's sample of what landed in its DRAM
+// (the last pass's pattern at kHostLinkSamples evenly spaced chunks plus the first and the last:
+// the GPU's stores reached host memory, not a device-side cache) -> the "hostLink" block.
+std::string finish_host_link(DeviceCtx& c, const hostlink::Plan& pl, bool* ok_out) {
+  unsigned long long bad_bits = 0, first_bad = ~0ull;
+  float write_ms = 0, read_ms = 0;
+  for (int pi = 0; pi < pl.patterns; ++pi) {
+    float w, r;
+    PROBE_CHECK(hipEventElapsedTime(&w, c.hev[2 * pi], c.hev[1 + 2 * pi]));
+    PROBE_CHECK(hipEventElapsedTime(&r, c.hev[1 + 2 * pi], c.hev[2 + 2 * pi]));
+    write_ms += w;
+    read_ms += r;
+    bad_bits += c.hl_res[2 * pi];
+    first_bad = std::min(first_bad, c.hl_res[2 * pi + 1]);
+  }
+  uint64_t samples = 0, sample_bad = 0;
+  if (!pl.preload) {
+    const uint32_t flip = ((pl.patterns - 1) & 1) ? 0xFFFFFFFFu : 0u;
+    const auto* host = static_cast<const uint32_t*>(c.hl_buf);
+    auto sample = [&](uint64_t j) {
+      const u32x4 e = pattern16<kHbmPattern>(j, pl.seed, flip);
+      const uint32_t* h = host + j * 4;
+      ++samples;
+      if (h[0] != e.x || h[1] != e.y || h[2] != e.z || h[3] != e.w) ++sample_bad;
+    };
+    if (pl.n16 <= static_cast<uint64_t>(kHostLinkSamples) + 2) {
+      for (uint64_t j = 0; j < pl.n16; ++j) sample(j);
+    } else {
+      sample(0);
+      for (int k = 0; k < kHostLinkSamples; ++k) sample(1 + (pl.n16 - 2) * static_cast<uint64_t>(k) / kHostLinkSamples);
+      sample(pl.n16 - 1);
+    }
+  }
+  const double moved = static_cast<double>(pl.n16) * 16.0 * pl.patterns;
+  const double write_gbps = !pl.preload && write_ms > 0 ? moved / (write_ms * 1e-3) / 1e9 : 0.0;
+  const double read_gbps = read_ms > 0 ? moved / (read_ms * 1e-3) / 1e9 : 0.0;
+  const double gbps = pl.preload ? read_gbps : std::min(write_gbps, read_gbps);
+  const bool ok = bad_bits == 0 && sample_bad == 0;
+  *ok_out = ok;
+  return "{\"ok\":" + std::string(ok ? "true" : "false") + ",\"bytes\":" + std::to_string(pl.n16 * 16) +
+         ",\"patterns\":" + std::to_string(pl.patterns) + ",\"seed\":" + std::to_string(pl.seed) +
+         ",\"badBits\":" + std::to_string(bad_bits) +
+         ",\"firstBadOffset\":" + (first_bad == ~0ull ? std::string("null") : std::to_string(first_bad * 16)) +
+         ",\"hostSamples\":" + std::to_string(samples) + ",\"hostSampleMismatches\":" + std::to_string(sample_bad) +
+         ",\"writeGBps\":" + jnum(write_gbps) + ",\"readGBps\":" + jnum(read_gbps) + ",\"GBps\":" + jnum(gbps) +
+         ",\"ms\":" + jnum((pl.preload ? 0.0 : write_ms) + read_ms) + ",\"allocMs\":" + jnum(pl.alloc_ms) + "}";
+}
+
 std::string run_probe(int dev, const char* opts) {
   const uint64_t hbm_bytes = static_cast<uint64_t>(opt_int(opts, "hbmBytes", 1LL << 30));
   const bool do_mfma = opt_int(opts, "mfma", 1) != 0;
@@ -1349,6 +1492,11 @@ std::string run_probe(int dev, const char* opts) {
   // The HBM test is bandwidth-bound with few waves per CU; the MFMA phase is compute-bound and
   // touches ~130 MiB: run them concurrently on two streams (overlap=0: one stream, serial).
   const bool overlap = opt_int(opts, "overlap", 1) != 0;
+  // host-link phase (hostlink.h), opt-in: 0 / absent = off
+  const uint64_t hl_bytes = static_cast<uint64_t>(std::max(0LL, opt_int(opts, "hostLinkBytes", 0)));
+  if (hl_bytes > kHostLinkMaxBytes) throw ProbeError("hostLinkBytes above 4 GiB");
+  hostlink::Plan hl;  // n16 == 0: off, and none of its options is looked up
+  if (hl_bytes) hl = host_link_plan(dev, opts, hl_bytes);
   auto t0 = std::chrono::steady_clock::now();
   PROBE_CHECK(hipSetDevice(dev));
   DeviceCtx& ctx = g_ctx[static_cast<size_t>(dev)];
@@ -1370,6 +1518,19 @@ std::string run_probe(int dev, const char* opts) {
                               lowp::kDtypes * lowp::kSlots * sizeof(unsigned long long)));
   }
   hipStream_t s = ctx.stream;
+  // With overlap the host-link phase has a stream of its own ("hostLinkStream":1: the tail of the
+  // MFMA stream instead, for the A/B), made like its buffer by the first probe that asks; serial
+  // (floors), it runs last on the one stream, alone on the GPU.
+  hipStream_t hl_s = s;
+  if (hl.n16) {
+    hl.alloc_ms = ensure_host_link(ctx, hl.n16 * 16, hl.coherent);
+    if (overlap && opt_int(opts, "hostLinkStream", 0) == 1) {
+      hl_s = ctx.stream2;
+    } else if (overlap) {
+      if (!ctx.hl_stream) PROBE_CHECK(hipStreamCreateWithFlags(&ctx.hl_stream, hipStreamNonBlocking));
+      hl_s = ctx.hl_stream;
+    }
+  }
   const hipDeviceProp_t& prop = ctx.prop;
   const int cus = prop.multiProcessorCount;
   auto ms_since = [](std::chrono::steady_clock::time_point a) {
@@ -1530,6 +1691,8 @@ std::string run_probe(int dev, const char* opts) {
                       ctx, s2);
     launch_lowp();
   }
+  // after the HBM kernels and the MFMA phase, so it overlaps both
+  if (hl.n16) launch_host_link(ctx, hl_s, hl);
   const double launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
   PROBE_CHECK(hipStreamSynchronize(s));
   const double hbm_wall_ms = ms_since(t_run);
@@ -1570,6 +1733,12 @@ std::string run_probe(int dev, const char* opts) {
                  ",\"cusVerified\":" + std::to_string(verified) + ",\"badWaves\":" + std::to_string(r[lowp::kSlotCensusBad]) + "}";
   }
   const double mfma_wall_ms = do_mfma ? ms_since(t_run) : 0.0;
+  bool hl_ok = true;
+  std::string hl_json;
+  if (hl.n16) {
+    if (hl_s != s && !(hl_s == ctx.stream2 && do_mfma)) PROBE_CHECK(hipStreamSynchronize(hl_s));
+    hl_json = finish_host_link(ctx, hl, &hl_ok);
+  }
   unsigned long long bad_bits = 0, first_bad = ~0ull;
   float write_ms = 0, read_ms = 0;
   for (int pi = 0; pi < patterns; ++pi) {
@@ -1599,7 +1768,7 @@ std::string run_probe(int dev, const char* opts) {
   out += "{\"device\":" + std::to_string(dev);
   out += ",\"hipUUID\":" + jstr(ctx.uuid);
   out += ",\"gcnArch\":" + jstr(prop.gcnArchName);
-  out += ",\"passed\":" + std::string(hbm_ok && mfma_ok && lowp_ok ? "true" : "false");
+  out += ",\"passed\":" + std::string(hbm_ok && mfma_ok && lowp_ok && hl_ok ? "true" : "false");
   out += ",\"hbm\":{\"ok\":" + std::string(hbm_ok ? "true" : "false") + ",\"bytes\":" + std::to_string(n16 * 16) +
          ",\"patterns\":" + std::to_string(patterns) + ",\"badBits\":" + std::to_string(bad_bits) +
          ",\"firstBadOffset\":" + (first_bad == ~0ull ? std::string("null") : std::to_string(first_bad * 16)) +
@@ -1624,6 +1793,7 @@ std::string run_probe(int dev, const char* opts) {
     out += "}";
   }
   if (lowp_mask) out += ",\"lowp\":{" + lowp_json + "}";
+  if (hl.n16) out += ",\"hostLink\":" + hl_json;
   out += ",\"ms\":" + jnum(total_ms);
   out += ",\"phases\":{\"arenaReused\":" + std::string(reused ? "true" : "false") +
          ",\"setupMs\":" + jnum(setup_ms) + ",\"allocMs\":" + jnum(alloc_ms) + ",\"launchMs\":" + jnum(launch_ms) +
@@ -2102,7 +2272,8 @@ char* mi355x_probe_peer_ring(const int* devs, int n, const char* opts_json) {
 
 // Frees the probe arenas idle for at least ``idle_ms`` (0: all, unconditionally); returns how many
 // were freed. With idle_ms > 0 an arena stays while its device holds an HBM sweep buffer or freed one
-// less than kSweepClearGrace ago.
+// less than kSweepClearGrace ago. The host-link phase's pinned buffer stays: trim hands VRAM back to
+// a tenant, and that is a few MiB of host RAM.
 int mi355x_probe_trim(int idle_ms) {
   if (g_count <= 0) return 0;
   int freed = 0;
@@ -2245,6 +2416,45 @@ int mi355x_probe_gemm_lowp(int dev, int dtype, const void* A, const void* Bt, co
   } catch (const std::exception&) {
     (void)hipGetLastError();
     return -4;
+  }
+}
+
+void mi355x_probe_host_link_geometry(int* grid, int* threads, int* unroll) {
+  if (grid) *grid = hostlink::kGrid;
+  if (threads) *threads = hostlink::kThreads;
+  if (unroll) *unroll = hostlink::kUnroll;
+}
+
+char* mi355x_probe_host_link(int dev, const char* opts_json, void* io, size_t io_bytes) {
+  if (g_count < 0 || dev < 0 || dev >= g_count) return dup("{\"passed\":false,\"error\":\"bad device index\"}");
+  const bool preload = opt_int(opts_json, "preload", 0) != 0;
+  if (preload && !io) return dup("{\"passed\":false,\"error\":\"preload needs a caller buffer\"}");
+  ProbeActive active;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  try {
+    DeviceCtx& ctx = g_ctx[static_cast<size_t>(dev)];
+    if (!ctx.ready) (void)run_probe(dev, "{\"hbmBytes\":1048576,\"patterns\":1,\"mfma\":false}");  // streams, events
+    PROBE_CHECK(hipSetDevice(dev));
+    const uint64_t bytes = preload ? static_cast<uint64_t>(io_bytes)
+                                   : static_cast<uint64_t>(std::max(0LL, opt_int(opts_json, "hostLinkBytes", 0)));
+    if (bytes < 16 || bytes > kHostLinkMaxBytes) throw ProbeError("host-link size outside [16 B, 4 GiB]");
+    hostlink::Plan pl = host_link_plan(dev, opts_json, bytes);
+    if (preload) {
+      pl.preload = true;
+      pl.patterns = 1;
+    }
+    pl.alloc_ms = ensure_host_link(ctx, pl.n16 * 16, pl.coherent);
+    if (preload) std::memcpy(ctx.hl_buf, io, pl.n16 * 16);
+    launch_host_link(ctx, ctx.stream, pl);
+    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
+    bool ok = true;
+    const std::string block = finish_host_link(ctx, pl, &ok);
+    if (io) std::memcpy(io, ctx.hl_buf, std::min<uint64_t>(io_bytes, pl.n16 * 16));
+    // the block is the whole report, with the usual head
+    return dup("{\"device\":" + std::to_string(dev) + ",\"passed\":" + (ok ? "true" : "false") + "," + block.substr(1));
+  } catch (const std::exception& e) {
+    (void)hipGetLastError();
+    return dup(std::string("{\"device\":") + std::to_string(dev) + ",\"passed\":false,\"error\":" + jstr(e.what()) + "}");
   }
 }
 

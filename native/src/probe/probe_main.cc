@@ -1,5 +1,5 @@
 // mi355x-probe CLI: `mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma]
-// [--low-precision fp8,mxfp8,mxfp4] [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
+// [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
 // Equivalent of the reference's in-pod `nvidia-smi` smoke check (GPU调度平台搭建.md:134-138),
 // but it exercises HBM and the matrix cores instead of only enumerating the device.
 #include <algorithm>
@@ -18,6 +18,7 @@ int main(int argc, char** argv) {
   bool mfma = true, all = true, list = false;
   int device = -1;
   int lowp_mask = 0;  // "mfmaLowPrecision": bit 0 fp8, 1 mxfp8, 2 mxfp4
+  long long host_link = 0;  // "hostLinkBytes": the PCIe host-link phase (0 = off)
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -52,10 +53,12 @@ int main(int argc, char** argv) {
         }
         p = q + 1;
       }
+    } else if (a == "--host-link-bytes") {
+      host_link = std::atoll(next());
     } else if (a == "--list") {
       list = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--low-precision fp8,mxfp8,mxfp4] [--list]\n");
+      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--list]\n");
       return 0;
     } else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -90,12 +93,13 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  char opts[256];
-  if (lowp_mask)
-    std::snprintf(opts, sizeof opts, "{\"hbmBytes\":%lld,\"mfma\":%s,\"gemmN\":%d,\"mfmaLowPrecision\":%d}", hbm,
-                  mfma ? "true" : "false", gemm_n, lowp_mask);
-  else
-    std::snprintf(opts, sizeof opts, "{\"hbmBytes\":%lld,\"mfma\":%s,\"gemmN\":%d}", hbm, mfma ? "true" : "false", gemm_n);
+  // optional keys only when asked for: the plain command line sends the options it always sent
+  std::string opts_s = "{\"hbmBytes\":" + std::to_string(hbm) + ",\"mfma\":" + (mfma ? "true" : "false") +
+                       ",\"gemmN\":" + std::to_string(gemm_n);
+  if (lowp_mask) opts_s += ",\"mfmaLowPrecision\":" + std::to_string(lowp_mask);
+  if (host_link > 0) opts_s += ",\"hostLinkBytes\":" + std::to_string(host_link);
+  opts_s += "}";
+  const char* opts = opts_s.c_str();
   std::vector<std::string> results(devs.size());
   std::vector<std::thread> ths;
   for (size_t i = 0; i < devs.size(); ++i) {

@@ -93,6 +93,8 @@ Json DeviceView::status_json() const {
         if (kv.second["ok"].as_bool(false)) verified.push_back(kv.first);
       p["lowPrecisionVerified"] = verified;
     }
+    if (probe["hostLink"].is_object())  // spec.probe.hostLinkCheck: the slower direction of the PCIe test
+      p["hostLinkGBps"] = probe.path("hostLink.GBps");
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)

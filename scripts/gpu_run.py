@@ -97,6 +97,11 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # lowp_claim_probe_cost.py --parent-lib DIR by hand for the default-path A/B)
         "lowp": [("lowp_gemm_rates", [PY, "scripts/gemm_lowp_rates.py"], 300, {}),
                  ("lowp_claim_probe_cost", [PY, "scripts/lowp_claim_probe_cost.py"], 600, {})],
+        # spec.probe.hostLinkCheck: the PCIe phase's rates and launch-shape sweep, its cost in the
+        # claim probe (give hostlink_claim_probe_cost.py --parent-lib DIR by hand for the
+        # default-path A/B)
+        "hostlink": [("hostlink_rates", [PY, "scripts/hostlink_rates.py"], 400, {}),
+                     ("hostlink_claim_probe_cost", [PY, "scripts/hostlink_claim_probe_cost.py"], 600, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],
