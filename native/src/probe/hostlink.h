@@ -1,7 +1,7 @@
 // Host-link (PCIe) phase of the probe, opt-in with "hostLinkBytes": the GPU writes the HBM test's
 // address-dependent pattern into pinned host memory over the link (device -> host), reads it back
-// over the link (host -> device) and verifies every bit, in both polarities. Included by probe.hip
-// after the HBM kernels, whose pattern16<kHbmPattern>, mismatches16, umin64 and reset_pairs it shares.
+// over the link (host -> device) and verifies every bit, in both polarities. Shares the HBM test's
+// pattern16<kHbmPattern>, mismatches16, umin64 and reset_pairs (hbm.h) and the fold of its passes.
 //
 // Shaped for the link, not for HBM: the link moves ~63 GB/s per direction (Gen5 x16) with
 // microseconds of latency, a hundredth of what hbm_fill / hbm_verify are laid out for, and the phase
@@ -11,31 +11,22 @@
 // kUnroll independent 16-byte accesses in flight to cover the link's latency.
 #pragma once
 
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdint>
+
+#include "arena.h"    // align4k
+#include "ctx.h"      // DeviceCtx: the phase's stream, events, counters and pinned buffer
+#include "hbm.h"      // pattern16, mismatches16, umin64, reset_pairs, fold_passes
+#include "report.h"   // HostLinkResult
+#include "options.h"  // hostlink::Plan and the measured defaults of its options
+#include "types.h"
+
+namespace {
 namespace hostlink {
 
 constexpr int kThreads = 256;
-// Grid, unroll, temporal / non-temporal access and coherent (fine-grained) / default pinned memory:
-// the probe options "hostLinkGrid", "hostLinkUnroll" (4 | 8 | 16), "hostLinkNT", "hostLinkCoherent"
-// select per run for the sweep of scripts/hostlink_rates.py. Measured on the MI355X at 64 MiB, alone
-// on the GPU, p50 GB/s write / read (profiles/hostlink_rates.json; PCIe Gen5 x16, 63 GB/s spec):
-//   * grid: the read needs 16 workgroups to fill the link — 2: 14.0, 4: 28.0, 8: 50.0, 16: 57.2,
-//     32: 55.3, 64..256: 56.2-57.1 (unroll 8); the write is at 53-56 from 2 workgroups on. 16
-//     workgroups are all the phase takes from the HBM and MFMA phases beside it.
-//   * unroll 4 / 8 / 16 at grid 16: 55.7 / 56.1 / 56.2 write, 57.3 / 57.2 / 57.1 read: flat. 8 keeps
-//     128 B per lane in flight; at grid 8 only unroll 4 still reads at 57.2 (8: 50.0, 16: 48.5).
-//   * temporal stores write 56.1 vs 55.0 non-temporal (56.2 vs 53.8 in an earlier run of the same
-//     sweep); loads are the same either way (57.18 vs 57.20). The opposite of the HBM kernels'
-//     choice: the data leaves the device whatever the hint says.
-//   * coherent (fine-grained) vs default pinned memory: 56.13 / 57.18 vs 56.07 / 57.17, no
-//     difference, and no configuration exceeded the link's rate (nothing is served from a cache).
-//     Coherent is kept: the host's sample and the flip hook then need no cache maintenance.
-// By size at these defaults: 1 MiB 45.2 / 44.3, 4 MiB 51.0 / 53.5, 16 MiB 53.1 / 56.3, 64 MiB
-// 56.1 / 57.2, 256 MiB 56.8 / 57.4; run-to-run spread under 0.2 GB/s from 8 MiB up.
-constexpr int kGrid = 16;
-constexpr int kUnroll = 8;
-constexpr bool kNonTemporal = false;
-constexpr bool kCoherent = true;
-constexpr int kMaxGrid = 1024;
 
 template <bool kNT>
 __device__ __forceinline__ void store16(u32x4* p, u32x4 v) {
@@ -109,18 +100,6 @@ __global__ __launch_bounds__(kThreads) void hostlink_verify(const u32x4* __restr
   }
 }
 
-// What one run of the phase does (options of mi355x_probe_run / mi355x_probe_host_link).
-struct Plan {
-  uint64_t n16 = 0;
-  int patterns = 2;
-  uint32_t seed = 0;
-  long long inject_chunk = -1;  // test hook "injectHostLinkFlipAtChunk"
-  bool preload = false;         // no write pass: verify what the caller loaded, polarity 0
-  int grid = kGrid, unroll = kUnroll;
-  bool nt = kNonTemporal, coherent = kCoherent;
-  double alloc_ms = 0;
-};
-
 inline int grid_for(const Plan& pl) {
   const uint64_t blocks = (pl.n16 + kThreads - 1) / kThreads;
   return static_cast<int>(std::max<uint64_t>(1, std::min<uint64_t>(static_cast<uint64_t>(pl.grid), blocks)));
@@ -168,4 +147,98 @@ inline void launch_verify(hipStream_t s, const Plan& pl, const u32x4* p, uint32_
           : launch_verify_as<8, false>(s, g, p, pl.n16, pl.seed, flip, bad_bits, first_bad);
 }
 
+// ------------------------------------------------------------------ the phase: ensure / launch / finish
+constexpr int kSamples = 1024;
+
+// Makes the phase's events, counters and a pinned, device-mapped buffer of at least ``bytes``.
+// The only place the buffer is freed or replaced: the caller holds the device's probe lock, and
+// every stream a kernel with the old pointer could be on is drained first. Returns the cost of the
+// pinned allocation when this call made or grew it, else 0.
+inline double ensure(DeviceCtx& c, uint64_t bytes, bool coherent) {
+  if (!c.hl_res) {  // set last: a failure half way is picked up by the next probe that asks
+    for (auto& e : c.hev)
+      if (!e) PROBE_CHECK(hipEventCreate(&e));
+    if (!c.hl_cnt)
+      PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.hl_cnt), 2 * kMaxPatterns * sizeof(unsigned long long)));
+    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.hl_res), 2 * kMaxPatterns * sizeof(unsigned long long)));
+  }
+  if (c.hl_buf && c.hl_bytes >= bytes && c.hl_coherent == coherent) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (c.hl_buf) {
+    if (c.hl_stream) PROBE_CHECK(hipStreamSynchronize(c.hl_stream));
+    PROBE_CHECK(hipStreamSynchronize(c.stream));
+    PROBE_CHECK(hipStreamSynchronize(c.stream2));
+    void* old = c.hl_buf;
+    c.hl_buf = c.hl_dev = nullptr;
+    c.hl_bytes = 0;
+    PROBE_CHECK(hipHostFree(old));
+  }
+  void* host = nullptr;
+  void* devp = nullptr;
+  const uint64_t cap = align4k(bytes);
+  PROBE_CHECK(hipHostMalloc(&host, cap, hipHostMallocMapped | (coherent ? hipHostMallocCoherent : hipHostMallocNonCoherent)));
+  if (hipHostGetDevicePointer(&devp, host, 0) != hipSuccess || !devp) {
+    (void)hipHostFree(host);
+    throw ProbeError("hipHostGetDevicePointer failed for the host-link buffer");
+  }
+  c.hl_buf = host;
+  c.hl_dev = devp;
+  c.hl_bytes = cap;
+  c.hl_coherent = coherent;
+  return ms_since(t0);
+}
+
+// Enqueues the phase on stream s: per pass a write (device -> host), an event, a verify (host ->
+// device), an event; then the counters' copy. No host synchronise, except for the flip hook.
+inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
+  auto* buf = static_cast<u32x4*>(c.hl_dev);
+  PROBE_CHECK(hipEventRecord(c.hev[0], s));
+  for (int pi = 0; pi < pl.patterns; ++pi) {
+    const uint32_t flip = PatternPass::flip_of(pi);
+    unsigned long long* reset = pi == 0 ? c.hl_cnt : nullptr;
+    // a preload keeps the caller's data: the write kernel only resets the counters (n16 = 0)
+    launch_write(s, pl, buf, pl.preload ? 0 : pl.n16, flip, reset, reset ? pl.patterns : 0);
+    PROBE_CHECK(hipEventRecord(c.hev[1 + 2 * pi], s));
+    if (pi == 0 && pl.inject_chunk >= 0 && static_cast<uint64_t>(pl.inject_chunk) < pl.n16) {
+      // test hook: the HOST flips bit 0 of a chunk once the write pass has landed
+      PROBE_CHECK(hipStreamSynchronize(s));
+      static_cast<volatile uint32_t*>(c.hl_buf)[static_cast<uint64_t>(pl.inject_chunk) * 4] ^= 1u;
+      std::atomic_thread_fence(std::memory_order_seq_cst);
+    }
+    launch_verify(s, pl, buf, flip, c.hl_cnt + 2 * pi, c.hl_cnt + 2 * pi + 1);
+    PROBE_CHECK(hipEventRecord(c.hev[2 + 2 * pi], s));
+  }
+  PROBE_CHECK(hipGetLastError());
+  PROBE_CHECK(hipMemcpyAsync(c.hl_res, c.hl_cnt, 2 * pl.patterns * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+}
+
+// After the stream's synchronise: the passes' fold and the host's sample of what landed in its DRAM
+// (the last pass's pattern at kSamples evenly spaced chunks plus the first and the last: the GPU's
+// stores reached host memory, not a device-side cache) -> the "hostLink" block's result.
+inline HostLinkResult finish(DeviceCtx& c, const Plan& pl) {
+  HostLinkResult r;
+  r.passes = fold_passes(c.hev, c.hl_res, pl.patterns, pl.n16);
+  r.seed = pl.seed;
+  r.preload = pl.preload;
+  r.alloc_ms = pl.alloc_ms;
+  if (pl.preload) return r;
+  const uint32_t flip = PatternPass::flip_of(pl.patterns - 1);
+  const auto* host = static_cast<const uint32_t*>(c.hl_buf);
+  auto sample = [&](uint64_t j) {
+    const u32x4 e = pattern16<kHbmPattern>(j, pl.seed, flip);
+    const uint32_t* h = host + j * 4;
+    ++r.samples;
+    if (h[0] != e.x || h[1] != e.y || h[2] != e.z || h[3] != e.w) ++r.sample_bad;
+  };
+  if (pl.n16 <= static_cast<uint64_t>(kSamples) + 2) {
+    for (uint64_t j = 0; j < pl.n16; ++j) sample(j);
+  } else {
+    sample(0);
+    for (int k = 0; k < kSamples; ++k) sample(1 + (pl.n16 - 2) * static_cast<uint64_t>(k) / kSamples);
+    sample(pl.n16 - 1);
+  }
+  return r;
+}
+
 }  // namespace hostlink
+}  // namespace

@@ -2,9 +2,9 @@
 // the block-scaled one (E8M0 scale per 32 K-elements). Opt-in ("mfmaLowPrecision"): none of this
 // is launched, and no memory is reserved for it, unless a probe asks for a dtype.
 //
-// Included by probe.hip inside its anonymous namespace, after the checksum kernels: uses its
-// f32x4 / u32x4 / lds_void_t types, pattern_word, cu_key / mark_cu, kCensusThreads, xcd_remap
-// (tile_order.h) and the fp32 instantiations of colsum_partial / rowdot, count_diff, count_ne_u32.
+// Uses the probe's f32x4 / u32x4 / lds_void_t types, pattern_word (hbm.h), cu_key / mark_cu /
+// kCensusThreads (census.h), xcd_remap (tile_order.h) and abft.h's fp32 instantiations of
+// colsum_partial / rowdot, count_diff and count_ne_u32.
 //
 // Per dtype: a per-CU census on that dtype's instruction, a 256^3 GEMM checked element by element
 // against a VALU reference that decodes the formats with integer bit arithmetic, and the N^3 GEMM
@@ -25,10 +25,21 @@
 // C/D: col = lane&15, row = 4(lane>>4) + j, as for bf16.
 #pragma once
 
-namespace lowp {
+#include <cstddef>
+#include <cstdint>
+#include <vector>
 
-enum Dtype { kFp8 = 0, kMxFp8 = 1, kMxFp4 = 2, kDtypes = 3 };
-constexpr const char* kNames[kDtypes] = {"fp8", "mxfp8", "mxfp4"};
+#include "abft.h"
+#include "arena.h"  // align4k, lowp::region_bytes, the counter slots
+#include "census.h"
+#include "hbm.h"
+#include "options.h"  // lowp::Dtype, kNames
+#include "report.h"   // LowpResult
+#include "tile_order.h"
+#include "types.h"
+
+namespace {
+namespace lowp {
 
 using i32x8 = __attribute__((ext_vector_type(8))) int;
 
@@ -425,19 +436,8 @@ __global__ __launch_bounds__(256) void rowdot(const uint8_t* __restrict__ X, con
 __global__ void inject_fault(float* __restrict__ c, int64_t idx) { c[idx] += 1.0f; }  // test hook
 
 // ------------------------------------------------------------------ host side: one dtype's phase
-// Device counters of one dtype: element mismatches, ABFT mismatches, bad census waves, census map.
-constexpr int kSlotSmall = 0, kSlotAbft = 1, kSlotCensusBad = 2, kSlotCensusMap = 3, kSlots = kSlotCensusMap + kCuMapWords;
-constexpr int kSmallN = 256, kCensusIters = 128;
-
-inline size_t align4k(size_t x) { return (x + 4095) & ~static_cast<size_t>(4095); }
-
-// The operand / C region every asked-for dtype shares (they run one after the other on one stream),
-// sized for the largest (8-bit operands).
-inline size_t region_bytes(size_t n) {
-  const size_t n0 = kSmallN;
-  return 2 * align4k(n0 * n0) + 2 * align4k(n0 * n0 / 32) + 2 * align4k(n0 * n0 * 4) + 2 * align4k(n * n) +
-         2 * align4k(n * n / 32) + align4k(n * n * 4) + align4k(6 * n * 4);
-}
+// The dtype's counters (kSlot*) and the size of the region carved below (region_bytes): arena.h.
+constexpr int kCensusIters = 128;
 
 // Enqueues one dtype's checks on s (no host sync): the 256^3 GEMM against the VALU reference, the
 // timed N^3 GEMM (events e0, e1) with ABFT, the census. cnt: the dtype's kSlots counters, zeroed by
@@ -458,6 +458,7 @@ void launch_phase_t(hipStream_t s, int dtype, char* region, int gemm_n, int cus,
   uint8_t *a = carve(n * n), *b = carve(n * n), *sa = carve(n * n / 32), *sb = carve(n * n / 32);
   auto* c = reinterpret_cast<float*>(carve(n * n * 4));
   auto* v32 = reinterpret_cast<uint32_t*>(carve(6 * n * 4));
+  if (static_cast<size_t>(p - region) != region_bytes(n)) throw ProbeError("lowp region and its size disagree");
   uint32_t *vacol = v32, *vbcol = v32 + n, *vcolC = v32 + 2 * n, *vexpC = v32 + 3 * n, *vrowC = v32 + 4 * n,
            *vexpR = v32 + 5 * n;
   const int scale_lo = dtype == kMxFp4 ? 1 : 0;
@@ -522,4 +523,50 @@ inline void launch_phase(hipStream_t s, int dtype, char* region, int gemm_n, int
   else launch_phase_t<MxFp4>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject, census_fault_xcc, poison_c);
 }
 
+// What the phase needs of a probe: where its memory and events are, and the options.
+struct Phase {
+  int mask = 0;                         // dtypes asked for; 0: nothing is enqueued
+  char* region = nullptr;               // region_bytes(gemm_n), shared by the dtypes
+  unsigned long long* cnt = nullptr;    // kDtypes * kSlots device counters
+  unsigned long long* host = nullptr;   // their pinned copy
+  hipEvent_t (*ev)[2] = nullptr;        // per dtype: around the timed GEMM
+  int gemm_n = 0, cus = 0;
+  int inject_mask = 0, census_fault_xcc = -1;  // test hooks
+  bool poison_c = false;
+};
+
+// Follows the bf16 MFMA phase on its stream: one dtype after the other through the shared region,
+// their counters copied back together. No host sync.
+inline void launch(hipStream_t s, const Phase& ph) {
+  if (!ph.mask) return;
+  PROBE_CHECK(hipMemsetAsync(ph.cnt, 0, kDtypes * kSlots * sizeof(unsigned long long), s));
+  for (int d = 0; d < kDtypes; ++d)
+    if (ph.mask >> d & 1)
+      launch_phase(s, d, ph.region, ph.gemm_n, ph.cus, ph.cnt + d * kSlots, ph.ev[d][0], ph.ev[d][1],
+                   (ph.inject_mask >> d & 1) != 0, ph.census_fault_xcc, ph.poison_c);
+  PROBE_CHECK(hipGetLastError());
+  PROBE_CHECK(hipMemcpyAsync(ph.host, ph.cnt, kDtypes * kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+}
+
+// After the stream's synchronise: each dtype's report entry; any failure fails the probe.
+inline std::vector<LowpResult> finish(const Phase& ph, bool require_all_cus) {
+  std::vector<LowpResult> out;
+  for (int d = 0; d < kDtypes; ++d) {
+    if (!(ph.mask >> d & 1)) continue;
+    const unsigned long long* r = ph.host + d * kSlots;
+    LowpResult res;
+    res.name = kNames[d];
+    res.n = ph.gemm_n;
+    PROBE_CHECK(hipEventElapsedTime(&res.ms, ph.ev[d][0], ph.ev[d][1]));
+    res.small_bad = r[kSlotSmall];
+    res.abft_bad = r[kSlotAbft];
+    res.bad_waves = r[kSlotCensusBad];
+    res.verified = count_cus(r + kSlotCensusMap).total;
+    res.ok = res.small_bad == 0 && res.abft_bad == 0 && res.bad_waves == 0 && (!require_all_cus || res.verified >= ph.cus);
+    out.push_back(res);
+  }
+  return out;
+}
+
 }  // namespace lowp
+}  // namespace

@@ -1,0 +1,259 @@
+// The options of the probe's entry points, read once and up front: every key with its default and
+// its clamping, as plain structs. Pure host code (no HIP include), shared by probe.hip and the host
+// unit test (native/tests/test_probe_options.cc). The defaults that a measurement chose live here
+// with that measurement, next to the option that overrides them for an in-process A/B.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+namespace {
+
+// First occurrence of the quoted key; `true` / `false`, spaces after the colon, else strtoll.
+inline long long opt_int(const char* json, const char* key, long long def) {
+  if (!json) return def;
+  std::string pat = std::string("\"") + key + "\"";
+  const char* p = std::strstr(json, pat.c_str());
+  if (!p) return def;
+  p = std::strchr(p + pat.size(), ':');
+  if (!p) return def;
+  ++p;
+  while (*p == ' ') ++p;
+  if (std::strncmp(p, "true", 4) == 0) return 1;
+  if (std::strncmp(p, "false", 5) == 0) return 0;
+  return std::strtoll(p, nullptr, 10);
+}
+
+inline bool opt_bool(const char* json, const char* key, bool def) { return opt_int(json, key, def) != 0; }
+
+constexpr long long kMaxPatterns = 4;
+
+// Default pattern (probe option "hbmPattern" selects per run, for in-process A/B). Measured on
+// MI355X, 9 interleaved rounds (profiles/r3h_probe_pattern_ab.json): 1 GiB test 6.16 -> 6.41 TB/s
+// (write 5.77 -> 6.06, read 6.64 -> 6.76), claim-time probe (beside the MFMA phase) 0.98 -> 0.91 ms.
+constexpr int kHbmPattern = 1;
+// Grid-stride (0) measured faster than tiled (1) for the fill (6.03 vs 5.51 TB/s) and within 4 % for
+// the verify: claim-time probe 0.757 vs 0.772 ms (profiles/r4h_probe_hbm_layout_ab_rejected.json).
+constexpr int kHbmLayout = 0;
+// Grid per HBM kernel, workgroups per CU. Measured on MI355X (scripts/probe_hbm_sweep.py): the
+// streaming store kernel is fastest with few long-running waves per CU, the verify kernel with a
+// few more loads in flight; the old 8/CU for both was among the slowest settings.
+constexpr long long kHbmFillBlocksPerCU = 1, kHbmVerifyBlocksPerCU = 3;
+
+// Tile order of gemm_bf16_mfma_256: 0 row-major, > 1 grouped. Groups of 4 tile rows: 8192^3 1331 vs
+// 1118 TFLOP/s (+19 %), 4096^3 unchanged (1366 vs 1372) (profiles/r4q_probe_gemm_group_ab.json).
+constexpr int kGemmGroupM = 4;
+// K-loop of the 256x256 GEMM ("gemmPipe" selects per probe): 0 the 2-phase loop, 1 the half-tile
+// pipeline, 2 the half-tile pipeline with staggered wave groups and a static s_setprio(1) for waves
+// 4-7 (default: 4096^3 1411 vs 1276 TFLOP/s for 0, 8192^3 1459 vs 1339, profiles/r6v_gemm_prio_ab.json),
+// 21 the same with s_setprio flips around every MFMA cluster instead (1358 / 1430; r6q, r6s), 22 with
+// no s_setprio, 3 the 32x32x16 fragment-ring variant (measured slower, r6t: A/B only). Also measured
+// and dropped: the phase reads as inline-asm ds_read_b128 in k-sub order with counted lgkmcnt, so a
+// quadrant's first MFMAs start on half its fragments (4096^3 1354 vs 1411, 8192^3 1420 vs 1456,
+// profiles/r6za_gemm_counted_reads_ab_rejected.json), and tile-row groups of 2/8/16 instead of 4
+// (r6z_gemm_group_ab.json).
+constexpr int kGemmPipe = 2;
+
+// Which GEMM kernel runs: the options "gemmTile", "gemmPipe", "gemmPrio", "gemmVecC".
+struct GemmVariant {
+  int tile = 256;        // 128: the older 128x128 register-staged kernel
+  int pipe = kGemmPipe;  // K-loop of the 256x256 kernel (see kGemmPipe)
+  bool prio = false;     // 2-phase loop only
+  bool vec_c = false;    // 2-phase loop only
+};
+
+// The GEMM options a probe and mi355x_probe_gemm_bf16_opts share. ``tile`` is what was asked for:
+// the host-buffer entry point refuses a tile that is neither 256 nor 128, a probe runs 256 then.
+struct GemmOptions {
+  GemmVariant variant;
+  int group_m = kGemmGroupM;  // tile order (A/B)
+  bool poison_c = false;      // test hook
+  static GemmOptions parse(const char* json) {
+    GemmOptions o;
+    o.variant.tile = static_cast<int>(opt_int(json, "gemmTile", 256));
+    o.variant.pipe = static_cast<int>(opt_int(json, "gemmPipe", kGemmPipe));
+    o.variant.prio = opt_bool(json, "gemmPrio", false);
+    o.variant.vec_c = opt_bool(json, "gemmVecC", false);
+    o.group_m = static_cast<int>(opt_int(json, "gemmGroupM", kGemmGroupM));
+    o.poison_c = opt_bool(json, "poisonC", false);
+    return o;
+  }
+};
+
+namespace lowp {
+// "mfmaLowPrecision" is a mask: bit d set asks for dtype d.
+enum Dtype { kFp8 = 0, kMxFp8 = 1, kMxFp4 = 2, kDtypes = 3 };
+constexpr const char* kNames[kDtypes] = {"fp8", "mxfp8", "mxfp4"};
+}  // namespace lowp
+
+namespace hostlink {
+
+// Grid, unroll, temporal / non-temporal access and coherent (fine-grained) / default pinned memory:
+// the probe options "hostLinkGrid", "hostLinkUnroll" (4 | 8 | 16), "hostLinkNT", "hostLinkCoherent"
+// select per run for the sweep of scripts/hostlink_rates.py. Measured on the MI355X at 64 MiB, alone
+// on the GPU, p50 GB/s write / read (profiles/hostlink_rates.json; PCIe Gen5 x16, 63 GB/s spec):
+//   * grid: the read needs 16 workgroups to fill the link — 2: 14.0, 4: 28.0, 8: 50.0, 16: 57.2,
+//     32: 55.3, 64..256: 56.2-57.1 (unroll 8); the write is at 53-56 from 2 workgroups on. 16
+//     workgroups are all the phase takes from the HBM and MFMA phases beside it.
+//   * unroll 4 / 8 / 16 at grid 16: 55.7 / 56.1 / 56.2 write, 57.3 / 57.2 / 57.1 read: flat. 8 keeps
+//     128 B per lane in flight; at grid 8 only unroll 4 still reads at 57.2 (8: 50.0, 16: 48.5).
+//   * temporal stores write 56.1 vs 55.0 non-temporal (56.2 vs 53.8 in an earlier run of the same
+//     sweep); loads are the same either way (57.18 vs 57.20). The opposite of the HBM kernels'
+//     choice: the data leaves the device whatever the hint says.
+//   * coherent (fine-grained) vs default pinned memory: 56.13 / 57.18 vs 56.07 / 57.17, no
+//     difference, and no configuration exceeded the link's rate (nothing is served from a cache).
+//     Coherent is kept: the host's sample and the flip hook then need no cache maintenance.
+// By size at these defaults: 1 MiB 45.2 / 44.3, 4 MiB 51.0 / 53.5, 16 MiB 53.1 / 56.3, 64 MiB
+// 56.1 / 57.2, 256 MiB 56.8 / 57.4; run-to-run spread under 0.2 GB/s from 8 MiB up.
+constexpr int kGrid = 16;
+constexpr int kUnroll = 8;
+constexpr bool kNonTemporal = false;
+constexpr bool kCoherent = true;
+constexpr int kMaxGrid = 1024;
+constexpr uint64_t kMaxBytes = 4ull << 30;
+
+// What one run of the phase does (options of mi355x_probe_run / mi355x_probe_host_link).
+struct Plan {
+  uint64_t n16 = 0;  // 0: the phase is off
+  int patterns = 2;
+  uint32_t seed = 0;
+  long long inject_chunk = -1;  // test hook "injectHostLinkFlipAtChunk"
+  bool preload = false;         // no write pass: verify what the caller loaded, polarity 0
+  int grid = kGrid, unroll = kUnroll;
+  bool nt = kNonTemporal, coherent = kCoherent;
+  double alloc_ms = 0;
+  // ``bytes``: "hostLinkBytes", or the caller's buffer for a preload.
+  static Plan parse(const char* json, int dev, uint64_t bytes) {
+    Plan pl;
+    pl.n16 = bytes / 16;
+    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "hostLinkPatterns", 2))));
+    pl.seed = 0x4C4B0000u + static_cast<uint32_t>(dev);
+    pl.inject_chunk = opt_int(json, "injectHostLinkFlipAtChunk", -1);
+    pl.grid = static_cast<int>(std::min<long long>(kMaxGrid, std::max(1LL, opt_int(json, "hostLinkGrid", kGrid))));
+    pl.unroll = static_cast<int>(opt_int(json, "hostLinkUnroll", kUnroll));
+    pl.nt = opt_bool(json, "hostLinkNT", kNonTemporal);
+    pl.coherent = opt_bool(json, "hostLinkCoherent", kCoherent);
+    return pl;
+  }
+};
+
+}  // namespace hostlink
+
+// Every option of mi355x_probe_run.
+struct ProbeOptions {
+  uint64_t hbm_bytes = 1ull << 30;
+  int patterns = 2;               // 1..kMaxPatterns
+  bool cheap_pattern = true;      // "hbmPattern" == 1
+  bool tiled = false;             // "hbmLayout" == 1, cheap pattern only
+  long long fill_blocks_per_cu = kHbmFillBlocksPerCU;  // "hbmFillBlocksPerCU", else "hbmBlocksPerCU"
+  long long verify_blocks_per_cu = kHbmVerifyBlocksPerCU;
+  int inject_flips = 0;           // test hook, 0..4096
+  long long inject_chunk = -1;    // test hook: one flip, bit 0 of a chunk
+  bool mfma = true;
+  int gemm_n = 4096;              // a multiple of 256, at least 256
+  GemmOptions gemm;               // variant.tile is 256 or 128 here
+  int reps = 1;                   // 0 with "gemmSkip" (test hook, with poisonC): C keeps the poison
+  int inject_gemm = 0;            // test hook
+  int census_fault_xcc = -1;      // test hook
+  bool require_all_cus = true;
+  bool cu_keys = false;
+  int lowp_mask = 0;              // bit d: also check lowp::Dtype d; needs the MFMA phase
+  int inject_lowp = 0;            // test hook: dtype mask
+  int lowp_census_fault_xcc = -1;
+  // The HBM test is bandwidth-bound with few waves per CU; the MFMA phase is compute-bound and
+  // touches ~130 MiB: run them concurrently on two streams (overlap=0: one stream, serial).
+  bool overlap = true;
+  // Launch order: the HBM test is the probe's critical path (~0.68 ms of kernels for 1 GiB x 2
+  // patterns); the MFMA phase (~0.1 ms of GPU time beside it) costs ~20 API calls to enqueue. With
+  // hbmFirst 1 the HBM kernels are enqueued first, so the fill starts ~20 launches earlier and the
+  // MFMA phase is enqueued while it runs (profiles/r4e_probe_launch_order_ab.json). 0: the MFMA
+  // phase first. 2: right after the first fill (in-process A/B), so it starts earlier on the GPU
+  // while the rest of the HBM test is still enqueued well ahead of need.
+  int hbm_first = 1;
+  // The first fill resets the HBM counter pairs and the MFMA phase's first kernel its own slots, so
+  // neither stream starts behind memsets or waits on the other — after an idle gap each API call
+  // ahead of the first fill costs tens of us (profiles/r4i_probe_idle_gap_ab.json). 0: memsets on
+  // the HBM stream, the MFMA stream waits for them (the older path).
+  bool zero_in_kernel = true;
+  bool keep_arena = true;
+  hostlink::Plan host_link;        // n16 == 0: off, and none of its options is looked up
+  bool host_link_on_mfma_stream = false;  // "hostLinkStream":1, for the A/B; only with overlap
+
+  static ProbeOptions parse(const char* json, int dev = 0) {
+    ProbeOptions o;
+    o.hbm_bytes = static_cast<uint64_t>(opt_int(json, "hbmBytes", 1LL << 30));
+    o.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "patterns", 2))));
+    o.cheap_pattern = opt_int(json, "hbmPattern", kHbmPattern) == 1;
+    o.tiled = o.cheap_pattern && opt_int(json, "hbmLayout", kHbmLayout) == 1;
+    o.fill_blocks_per_cu =
+        std::max(1LL, opt_int(json, "hbmFillBlocksPerCU", opt_int(json, "hbmBlocksPerCU", kHbmFillBlocksPerCU)));
+    o.verify_blocks_per_cu =
+        std::max(1LL, opt_int(json, "hbmVerifyBlocksPerCU", opt_int(json, "hbmBlocksPerCU", kHbmVerifyBlocksPerCU)));
+    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
+    o.mfma = opt_bool(json, "mfma", true);
+    o.gemm_n = std::max(256, (static_cast<int>(opt_int(json, "gemmN", 4096)) / 256) * 256);
+    o.gemm = GemmOptions::parse(json);
+    o.gemm.variant.tile = o.gemm.variant.tile != 128 ? 256 : 128;
+    o.reps = opt_int(json, "gemmSkip", 0) ? 0 : static_cast<int>(std::max(1LL, opt_int(json, "gemmReps", 1)));
+    o.inject_gemm = static_cast<int>(opt_int(json, "injectGemmFault", 0));
+    o.census_fault_xcc = static_cast<int>(opt_int(json, "injectCensusFaultXcc", -1));
+    o.require_all_cus = opt_bool(json, "requireAllCUs", true);
+    o.cu_keys = opt_bool(json, "cuKeys", false);
+    o.lowp_mask = o.mfma ? static_cast<int>(opt_int(json, "mfmaLowPrecision", 0)) & ((1 << lowp::kDtypes) - 1) : 0;
+    o.inject_lowp = static_cast<int>(opt_int(json, "injectLowpFault", 0));
+    o.lowp_census_fault_xcc = static_cast<int>(opt_int(json, "injectLowpCensusFaultXcc", -1));
+    o.overlap = opt_bool(json, "overlap", true);
+    o.hbm_first = static_cast<int>(opt_int(json, "hbmFirst", 1));
+    o.zero_in_kernel = opt_bool(json, "zeroInKernel", true);
+    o.keep_arena = opt_bool(json, "keepArena", true);
+    const uint64_t hl_bytes = static_cast<uint64_t>(std::max(0LL, opt_int(json, "hostLinkBytes", 0)));
+    if (hl_bytes > hostlink::kMaxBytes) throw std::invalid_argument("hostLinkBytes above 4 GiB");
+    if (hl_bytes) {
+      o.host_link = hostlink::Plan::parse(json, dev, hl_bytes);
+      o.host_link_on_mfma_stream = o.overlap && opt_int(json, "hostLinkStream", 0) == 1;
+    }
+    return o;
+  }
+};
+
+// mi355x_probe_host_link: "preload" verifies the caller's buffer, one pass, polarity 0.
+struct HostLinkOptions {
+  bool preload = false;
+  uint64_t bytes = 0;  // "hostLinkBytes" (ignored for a preload: the caller's buffer decides)
+  static HostLinkOptions parse(const char* json) {
+    HostLinkOptions o;
+    o.preload = opt_bool(json, "preload", false);
+    o.bytes = static_cast<uint64_t>(std::max(0LL, opt_int(json, "hostLinkBytes", 0)));
+    return o;
+  }
+};
+
+// "bytes" of mi355x_probe_peer (default 256 MiB) and mi355x_probe_peer_ring (64 MiB): at least 1 MiB.
+inline uint64_t peer_bytes(const char* json, long long def) {
+  return static_cast<uint64_t>(std::max(1LL << 20, opt_int(json, "bytes", def)));
+}
+
+// mi355x_probe_hbm_sweep.
+struct SweepOptions {
+  uint64_t bytes = 16ull << 30;   // window, at least 1 MiB
+  uint64_t reserve = 4ull << 30;  // free HBM left alone when the call has to allocate the buffer
+  uint64_t offset = 0;
+  bool keep = false;
+  int inject_flips = 0;  // test hook, 0..4096
+  static SweepOptions parse(const char* json) {
+    SweepOptions o;
+    o.bytes = static_cast<uint64_t>(std::max(1LL << 20, opt_int(json, "bytes", 16LL << 30)));
+    o.reserve = static_cast<uint64_t>(std::max(0LL, opt_int(json, "reserve", 4LL << 30)));
+    o.offset = static_cast<uint64_t>(std::max(0LL, opt_int(json, "offset", 0)));
+    o.keep = opt_bool(json, "keep", false);
+    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    return o;
+  }
+};
+
+}  // namespace

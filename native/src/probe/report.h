@@ -1,0 +1,257 @@
+// The text of every report the probe library returns: plain result structs in, JSON out. Key order
+// and number formatting are part of the interface (the agent and the tests parse them). Pure host
+// code (no HIP include): native/tests/test_probe_report.cc pins every block byte for byte.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+namespace {
+
+inline std::string jnum(double v) {
+  char b[64];
+  std::snprintf(b, sizeof b, "%.6g", v);
+  return b;
+}
+
+inline std::string jstr(const std::string& s) {
+  std::string o = "\"";
+  for (char c : s) {
+    if (c == '"' || c == '\\') o.push_back('\\');
+    if (static_cast<unsigned char>(c) < 0x20) continue;
+    o.push_back(c);
+  }
+  return o + "\"";
+}
+
+inline const char* jbool(bool b) { return b ? "true" : "false"; }
+
+// first_bad: a 16-byte chunk index, all-ones = none -> byte offset ``base + 16 * first_bad`` or null
+inline std::string joffset(unsigned long long first_bad, unsigned long long base = 0) {
+  return first_bad == ~0ull ? std::string("null") : std::to_string(base + first_bad * 16);
+}
+
+// A pattern test folded over its passes (hbm.h fold_passes): the HBM phase and the host link.
+struct HbmResult {
+  unsigned long long bad_bits = 0, first_bad = ~0ull;
+  float write_ms = 0, read_ms = 0;
+  uint64_t n16 = 0;
+  int patterns = 0;
+  bool ok() const { return bad_bits == 0; }
+};
+
+inline std::string hbm_block(const HbmResult& r) {
+  const double bytes_moved = static_cast<double>(r.n16) * 16.0 * r.patterns;
+  const double write_gbps = bytes_moved / (r.write_ms * 1e-3) / 1e9;
+  const double read_gbps = bytes_moved / (r.read_ms * 1e-3) / 1e9;
+  const double gbps = 2.0 * bytes_moved / ((r.write_ms + r.read_ms) * 1e-3) / 1e9;
+  return "{\"ok\":" + std::string(jbool(r.ok())) + ",\"bytes\":" + std::to_string(r.n16 * 16) +
+         ",\"patterns\":" + std::to_string(r.patterns) + ",\"badBits\":" + std::to_string(r.bad_bits) +
+         ",\"firstBadOffset\":" + joffset(r.first_bad) + ",\"writeGBps\":" + jnum(write_gbps) +
+         ",\"readGBps\":" + jnum(read_gbps) + ",\"GBps\":" + jnum(gbps) + ",\"ms\":" + jnum(r.write_ms + r.read_ms) + "}";
+}
+
+inline double gemm_tflops(int n, double ms) {
+  return ms > 0 ? 2.0 * n * static_cast<double>(n) * n / (ms * 1e-3) / 1e12 : 0.0;
+}
+
+struct MfmaResult {
+  bool ok = true, enabled = false;
+  int n = 0, tile = 256, pipe = 0;
+  unsigned long long small_bad = 0, abft_bad = 0;
+  double tflops = 0, ms = 0;
+};
+
+inline std::string mfma_block(const MfmaResult& r) {
+  return "{\"ok\":" + std::string(jbool(r.ok)) + ",\"enabled\":" + jbool(r.enabled) + ",\"n\":" + std::to_string(r.n) +
+         ",\"tile\":" + std::to_string(r.tile) + ",\"pipe\":" + std::to_string(r.pipe) +
+         ",\"elementMismatches\":" + std::to_string(r.small_bad) + ",\"abftMismatches\":" + std::to_string(r.abft_bad) +
+         ",\"tflops\":" + jnum(r.tflops) + ",\"ms\":" + jnum(r.ms) + "}";
+}
+
+// Which CUs proved their matrix cores (census) and which ran GEMM tiles.
+struct CusResult {
+  int expected = 0, verified = 0;
+  int per_xcd[8] = {};
+  int gemm_tiles = 0;
+  unsigned long long bad_waves = 0;
+  bool want_keys = false;  // "cuKeys": the (xcc, se, sh, cu) key of every verified CU
+  std::vector<int> keys;
+};
+
+inline std::string cus_block(const CusResult& r) {
+  std::string per = "[";
+  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
+  std::string out = "{\"expected\":" + std::to_string(r.expected) + ",\"mfmaVerified\":" + std::to_string(r.verified) +
+                    ",\"perXcd\":" + per + "]" + ",\"gemmTiles\":" + std::to_string(r.gemm_tiles) +
+                    ",\"badWaves\":" + std::to_string(r.bad_waves) + ",\"ok\":" +
+                    jbool(r.bad_waves == 0 && r.verified >= r.expected);
+  if (r.want_keys) {
+    out += ",\"cuKeys\":[";
+    for (size_t i = 0; i < r.keys.size(); ++i) out += (i ? "," : "") + std::to_string(r.keys[i]);
+    out += "]";
+  }
+  return out + "}";
+}
+
+struct LowpResult {
+  const char* name = "";
+  bool ok = true;
+  int n = 0;
+  unsigned long long small_bad = 0, abft_bad = 0;
+  float ms = 0;
+  int verified = 0;
+  unsigned long long bad_waves = 0;
+};
+
+// One entry per dtype that ran, in dtype order.
+inline std::string lowp_block(const std::vector<LowpResult>& rs) {
+  std::string out = "{";
+  for (const LowpResult& r : rs)
+    out += std::string(out.size() > 1 ? "," : "") + "\"" + r.name + "\":{\"ok\":" + jbool(r.ok) +
+           ",\"n\":" + std::to_string(r.n) + ",\"elementMismatches\":" + std::to_string(r.small_bad) +
+           ",\"abftMismatches\":" + std::to_string(r.abft_bad) + ",\"tflops\":" + jnum(gemm_tflops(r.n, r.ms)) +
+           ",\"ms\":" + jnum(r.ms) + ",\"cusVerified\":" + std::to_string(r.verified) +
+           ",\"badWaves\":" + std::to_string(r.bad_waves) + "}";
+  return out + "}";
+}
+
+// The host-link phase: the passes' fold plus the host's own sample of what landed in its DRAM.
+struct HostLinkResult {
+  HbmResult passes;
+  uint32_t seed = 0;
+  uint64_t samples = 0, sample_bad = 0;
+  bool preload = false;
+  double alloc_ms = 0;
+  bool ok() const { return passes.bad_bits == 0 && sample_bad == 0; }
+};
+
+inline std::string host_link_block(const HostLinkResult& r) {
+  const HbmResult& p = r.passes;
+  const double moved = static_cast<double>(p.n16) * 16.0 * p.patterns;
+  const double write_gbps = !r.preload && p.write_ms > 0 ? moved / (p.write_ms * 1e-3) / 1e9 : 0.0;
+  const double read_gbps = p.read_ms > 0 ? moved / (p.read_ms * 1e-3) / 1e9 : 0.0;
+  const double gbps = r.preload ? read_gbps : std::min(write_gbps, read_gbps);
+  return "{\"ok\":" + std::string(jbool(r.ok())) + ",\"bytes\":" + std::to_string(p.n16 * 16) +
+         ",\"patterns\":" + std::to_string(p.patterns) + ",\"seed\":" + std::to_string(r.seed) +
+         ",\"badBits\":" + std::to_string(p.bad_bits) + ",\"firstBadOffset\":" + joffset(p.first_bad) +
+         ",\"hostSamples\":" + std::to_string(r.samples) + ",\"hostSampleMismatches\":" + std::to_string(r.sample_bad) +
+         ",\"writeGBps\":" + jnum(write_gbps) + ",\"readGBps\":" + jnum(read_gbps) + ",\"GBps\":" + jnum(gbps) +
+         ",\"ms\":" + jnum((r.preload ? 0.0 : p.write_ms) + p.read_ms) + ",\"allocMs\":" + jnum(r.alloc_ms) + "}";
+}
+
+// Host wall-clock of a probe's steps.
+struct PhaseTimes {
+  bool arena_reused = false;
+  double setup_ms = 0, alloc_ms = 0, launch_ms = 0;
+  int hbm_first = 1;
+  double hbm_wall_ms = 0, mfma_wall_ms = 0, free_ms = 0;
+};
+
+inline std::string phases_block(const PhaseTimes& t) {
+  return "{\"arenaReused\":" + std::string(jbool(t.arena_reused)) + ",\"setupMs\":" + jnum(t.setup_ms) +
+         ",\"allocMs\":" + jnum(t.alloc_ms) + ",\"launchMs\":" + jnum(t.launch_ms) +
+         ",\"hbmFirst\":" + std::to_string(t.hbm_first) + ",\"hbmWallMs\":" + jnum(t.hbm_wall_ms) +
+         ",\"mfmaWallMs\":" + jnum(t.mfma_wall_ms) + ",\"freeMs\":" + jnum(t.free_ms) + "}";
+}
+
+// The head of a report about one device / one peer link; also what an error report starts with.
+inline std::string device_head(int dev) { return "\"device\":" + std::to_string(dev); }
+
+// Everything mi355x_probe_run reports. "cus" only with the MFMA phase, "lowp" only with a dtype,
+// "hostLink" only when asked for.
+struct ProbeReport {
+  int dev = 0;
+  std::string uuid, arch;
+  HbmResult hbm;
+  MfmaResult mfma;
+  CusResult cus;
+  std::vector<LowpResult> lowp;
+  bool has_host_link = false;
+  HostLinkResult host_link;
+  double total_ms = 0;
+  PhaseTimes phases;
+  bool passed() const {
+    bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok());
+    for (const LowpResult& l : lowp) ok = ok && l.ok;
+    return ok;
+  }
+};
+
+// The report up to and including "phases", unclosed: the caller appends "reportMs" (the host time
+// spent in here, timing of the binding) and the closing brace.
+inline std::string probe_report_open(const ProbeReport& r) {
+  std::string out;
+  out.reserve(2048);  // one allocation for the whole report
+  out += "{" + device_head(r.dev);
+  out += ",\"hipUUID\":" + jstr(r.uuid);
+  out += ",\"gcnArch\":" + jstr(r.arch);
+  out += ",\"passed\":" + std::string(jbool(r.passed()));
+  out += ",\"hbm\":" + hbm_block(r.hbm);
+  out += ",\"mfma\":" + mfma_block(r.mfma);
+  if (r.mfma.enabled) out += ",\"cus\":" + cus_block(r.cus);
+  if (!r.lowp.empty()) out += ",\"lowp\":" + lowp_block(r.lowp);
+  if (r.has_host_link) out += ",\"hostLink\":" + host_link_block(r.host_link);
+  out += ",\"ms\":" + jnum(r.total_ms);
+  out += ",\"phases\":" + phases_block(r.phases);
+  return out;
+}
+inline std::string link_head(int src, int dst) {
+  return "\"src\":" + std::to_string(src) + ",\"dst\":" + std::to_string(dst);
+}
+
+// ``head`` empty: a report with no head.
+inline std::string error_report(const std::string& head, const std::string& what) {
+  return "{" + head + (head.empty() ? "" : ",") + "\"passed\":false,\"error\":" + jstr(what) + "}";
+}
+
+// One xGMI link: mi355x_probe_peer's whole report and an entry of the ring's "links".
+struct PeerLink {
+  int src = 0, dst = 0;
+  std::string error;  // non-empty: no peer access
+  unsigned long long bad_bits = 0;
+  uint64_t bytes = 0;
+  float ms = 0;
+  bool ok() const { return error.empty() && bad_bits == 0; }
+};
+
+inline std::string peer_link_block(const PeerLink& l) {
+  if (!l.error.empty())
+    return "{" + link_head(l.src, l.dst) + ",\"canAccessPeer\":false,\"passed\":false,\"error\":" + jstr(l.error) + "}";
+  const double gbps = l.ms > 0 ? static_cast<double>(l.bytes) / (l.ms * 1e-3) / 1e9 : 0.0;
+  return "{" + link_head(l.src, l.dst) + ",\"canAccessPeer\":true,\"passed\":" + jbool(l.bad_bits == 0) +
+         ",\"badBits\":" + std::to_string(l.bad_bits) + ",\"bytes\":" + std::to_string(l.bytes) +
+         ",\"GBps\":" + jnum(gbps) + ",\"ms\":" + jnum(l.ms) + "}";
+}
+
+inline std::string peer_ring_report(uint64_t bytes, const std::vector<PeerLink>& links) {
+  std::string out = "{\"bytes\":" + std::to_string(bytes) + ",\"links\":[";
+  bool all_ok = true;
+  for (size_t i = 0; i < links.size(); ++i) {
+    all_ok = all_ok && links[i].ok();
+    out += (i ? "," : "") + peer_link_block(links[i]);
+  }
+  return out + "],\"passed\":" + jbool(all_ok) + "}";
+}
+
+// One window of the HBM sweep; first_bad counts 16-byte chunks from the window's start.
+struct SweepResult {
+  int dev = 0;
+  uint64_t offset = 0, bytes = 0, span = 0;
+  unsigned long long bad_bits = 0, first_bad = ~0ull;
+  float ms = 0;
+  double alloc_ms = 0;
+};
+
+inline std::string sweep_report(const SweepResult& r) {
+  const double gbps = r.ms > 0 ? 4.0 * static_cast<double>(r.bytes) / (r.ms * 1e-3) / 1e9 : 0.0;
+  return "{" + device_head(r.dev) + ",\"passed\":" + jbool(r.bad_bits == 0) + ",\"offset\":" + std::to_string(r.offset) +
+         ",\"bytes\":" + std::to_string(r.bytes) + ",\"span\":" + std::to_string(r.span) +
+         ",\"badBits\":" + std::to_string(r.bad_bits) + ",\"firstBadOffset\":" + joffset(r.first_bad, r.offset) +
+         ",\"GBps\":" + jnum(gbps) + ",\"ms\":" + jnum(r.ms) + ",\"allocMs\":" + jnum(r.alloc_ms) + "}";
+}
+
+}  // namespace

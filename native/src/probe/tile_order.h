@@ -1,4 +1,4 @@
-// Workgroup -> output tile mapping of the probe's GEMM kernels (probe.hip): pure integer functions,
+// Workgroup -> output tile mapping of the probe's GEMM kernels (gemm_bf16.h): pure integer functions,
 // shared by the kernels and the host unit test (native/tests/test_tile_order.cc).
 #pragma once
 
