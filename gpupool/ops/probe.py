@@ -65,6 +65,19 @@ def lib() -> ctypes.CDLL:
                                                      ctypes.c_size_t]
                 l.mi355x_probe_host_link_geometry.restype = None
                 l.mi355x_probe_host_link_geometry.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
+            if hasattr(l, "mi355x_probe_abft_check"):  # absent from a library built before them
+                vp, ull = ctypes.c_void_p, ctypes.c_ulonglong
+                l.mi355x_probe_abft_check.restype = ctypes.c_int
+                l.mi355x_probe_abft_check.argtypes = [ctypes.c_int, ctypes.c_int] + [vp] * 5 + \
+                    [ctypes.c_int] * 3 + [ctypes.c_float, vp, vp, ctypes.c_int, vp, vp, vp]
+                l.mi355x_probe_gemm_ref.restype = ctypes.c_int
+                l.mi355x_probe_gemm_ref.argtypes = [ctypes.c_int, ctypes.c_int] + [vp] * 5 + [ctypes.c_int] * 3
+                l.mi355x_probe_count_diff.restype = ctypes.c_int
+                l.mi355x_probe_count_diff.argtypes = [ctypes.c_int, vp, vp, ull, ctypes.POINTER(ull)]
+                l.mi355x_probe_gen_operands.restype = ctypes.c_int
+                l.mi355x_probe_gen_operands.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
+                                                        ull, ull, vp, ctypes.c_size_t, vp, ctypes.c_size_t,
+                                                        vp, ctypes.c_size_t]
             _lib = l
     return _lib
 
@@ -106,7 +119,9 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     host memory (written and read back by the GPU over the link, every bit verified, both
     directions timed), reported under "hostLink". ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
-    the device buffers between compute and check so tests can prove the checkers catch faults."""
+    the device buffers between compute and check so tests can prove the checkers catch faults;
+    injectGemmFaultRow / injectGemmFaultCol place the GEMM fault (and injectLowpFault's) at that
+    element of C instead of row gemm_n/3, column gemm_n/5 — outside C: no fault."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())),
                      tuple(mfma_low_precision), int(host_link_bytes))
@@ -273,3 +288,68 @@ def gemm_lowp(dev: int, dtype: str, a_ptr: int, bt_ptr: int, scale_a_ptr: int | 
         raise ValueError(f"mi355x_probe_gemm_lowp refused its arguments (rc={rc}): m, n, k must be "
                          f"multiples of 128, scales given exactly for the scaled dtypes and the "
                          f"device index valid")
+
+
+# ---------------------------------------------------------------- test surfaces of the checkers
+# The kernels that decide a probe's verdict, on caller HOST buffers (pointers as for gemm_lowp), so a
+# test can compare them with a host reference (tests/gpu/abft_cases.py). Not on the claim path.
+def _checker_dtype(dtype: str) -> int:
+    return -1 if dtype == "bf16" else lowp.dtype_index(dtype)
+
+
+def _checker_rc(name: str, rc: int) -> None:
+    if rc == -4:
+        raise RuntimeError(f"mi355x_probe_{name} failed with a HIP error (rc=-4)")
+    if rc != 0:
+        raise ValueError(f"mi355x_probe_{name} refused its arguments (rc={rc})")
+
+
+def _checker_lib():
+    if not hasattr(lib(), "mi355x_probe_abft_check"):
+        raise RuntimeError("libmi355x_probe.so predates the checker test surfaces: rebuild it")
+    return lib()
+
+
+def abft_check(dev: int, dtype: str, a_ptr: int, bt_ptr: int, scale_a_ptr: int | None,
+               scale_bt_ptr: int | None, c_ptr: int, m: int, n: int, k: int, bound: float,
+               vectors_ptr: int, counts_ptr: int, nfaults: int = 0, fault_index_ptr: int | None = None,
+               fault_value_ptr: int | None = None, fault_counts_ptr: int | None = None) -> None:
+    """The probe's ABFT checker sequence over A [m,k], Bt [n,k] (``dtype`` "bf16" or one of
+    ``lowp.DTYPES``) and the caller's C fp32 [m,n]. ``vectors_ptr``: 2k + 2n + 2m uint32 (column sums
+    of A, of Bt, of C, expected of C; row sums of C, expected), ``counts_ptr``: 3 uint64 (elements
+    that are no integer / not finite / beyond ``bound``, column mismatches, row mismatches).
+    ``nfaults`` > 0: per fault i, C[fault_index[i]] (int64, row * n + col) is set to fault_value[i]
+    (float32) on the device, the sequence runs, the element is put back; ``fault_counts_ptr``:
+    3 * nfaults uint64. bf16 k % 8 == 0, else k % 32 == 0; n % 4 == 0. A refused call (ValueError)
+    leaves every output untouched."""
+    _checker_rc("abft_check", _checker_lib().mi355x_probe_abft_check(
+        dev, _checker_dtype(dtype), a_ptr, bt_ptr, scale_a_ptr, scale_bt_ptr, c_ptr, m, n, k, bound,
+        vectors_ptr, counts_ptr, nfaults, fault_index_ptr, fault_value_ptr, fault_counts_ptr))
+
+
+def gemm_ref(dev: int, dtype: str, a_ptr: int, bt_ptr: int, scale_a_ptr: int | None,
+             scale_bt_ptr: int | None, r_ptr: int, m: int, n: int, k: int) -> None:
+    """The VALU reference of the probe's element check: R fp32 [m,n] = A x Bt^T, shapes and dtypes
+    as for ``abft_check``."""
+    _checker_rc("gemm_ref", _checker_lib().mi355x_probe_gemm_ref(
+        dev, _checker_dtype(dtype), a_ptr, bt_ptr, scale_a_ptr, scale_bt_ptr, r_ptr, m, n, k))
+
+
+def count_diff(dev: int, x_ptr: int, y_ptr: int, count: int) -> int:
+    """How many of ``count`` float32 elements the element check's comparer finds different."""
+    bad = ctypes.c_ulonglong(0)
+    _checker_rc("count_diff", _checker_lib().mi355x_probe_count_diff(dev, x_ptr, y_ptr, count,
+                                                                     ctypes.byref(bad)))
+    return int(bad.value)
+
+
+def gen_operands(dev: int, dtype: str, seed: int, span_or_scale_lo: int, count: int, nzero: int,
+                 operand_ptr: int, operand_bytes: int, scales_ptr: int | None = None,
+                 scale_bytes: int = 0, zero_ptr: int | None = None, zero_bytes: int = 0) -> None:
+    """The in-probe operand generator with its production grid, into device buffers that start as
+    0xFF bytes and come back whole: ``count`` elements ("bf16": integers in [-span, span]; low
+    precision: whole 32-bit words, count / 32 scale bytes for the scaled dtypes) and, bf16 only,
+    the first ``nzero`` words of the zero region zeroed."""
+    _checker_rc("gen_operands", _checker_lib().mi355x_probe_gen_operands(
+        dev, _checker_dtype(dtype), seed, span_or_scale_lo, count, nzero, operand_ptr, operand_bytes,
+        scales_ptr, scale_bytes, zero_ptr, zero_bytes))

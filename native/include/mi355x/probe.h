@@ -27,7 +27,10 @@ char* mi355x_probe_identify(int device);
  * wave, the CU identified by its XCC_ID/HW_ID registers); with requireAllCUs the probe fails
  * unless mfmaVerified >= the runtime's CU count. gemmTiles = CUs that ran tiles of the timed GEMM.
  * Test hooks (corrupt a buffer between compute and check): "injectBitFlips":N flips N bits spread
- * over the HBM region, "injectFlipAtChunk":i flips bit 0 of 16-byte chunk i, "injectGemmFault".
+ * over the HBM region, "injectFlipAtChunk":i flips bit 0 of 16-byte chunk i, "injectGemmFault":mode
+ * (1: +1.0, 2: +0.25, else NaN) at one element of the gemmN GEMM's C: "injectGemmFaultRow" /
+ * "injectGemmFaultCol", -1 (default) row gemmN/3 and column gemmN/5, any other value outside
+ * [0, gemmN) no fault. "injectLowpFault" strikes the same element.
  *
  * Low-precision matrix cores (opt-in): "mfmaLowPrecision":mask, bit 0 fp8 (OCP e4m3fn on
  * v_mfma_f32_16x16x32_fp8_fp8), bit 1 mxfp8 (e4m3) and bit 2 mxfp4 (e2m1), both on
@@ -118,6 +121,47 @@ int mi355x_probe_gemm_bf16_opts(int device, const void* A, const void* Bt, void*
  * dtype; C is not touched), -4 a HIP error. */
 int mi355x_probe_gemm_lowp(int device, int dtype, const void* A, const void* Bt, const void* scaleA,
                            const void* scaleBt, void* C, int m, int n, int k, const char* opts_json);
+/* Test surfaces: the kernels that decide a probe's verdict, on caller HOST buffers, so a test can
+ * compare them with a host reference. None of them is on the claim path; each allocates per call,
+ * frees on every path and leaves the probe's kept arena alone. dtype: -1 bf16 (2 bytes per element),
+ * else the low-precision index of mi355x_probe_gemm_lowp with its operand layouts; scaleA / scaleBt
+ * as there (NULL for bf16 and fp8). All return 0 = ok, -1 bad device, -2 bad arguments (no output is
+ * touched), -4 a HIP error.
+ *
+ * abft_check: the probe's ABFT checker sequence (same kernels, grids and order as a probe's) over
+ * A[m][k], Bt[n][k] and the caller's C[m][n] (fp32). bf16 needs k % 8 == 0, low precision k % 32 == 0;
+ * n % 4 == 0, 1 <= m, n, k <= 65535. bound: the largest |C| the operands allow. vectors: 2k + 2n + 2m
+ * words, packed: the column sums of A (k) and of Bt (k), the column sums of C (n) and what they
+ * must be (n), the row sums of C (m) and what they must be (m), all mod 2^32. counts[3]: elements
+ * of C that are no integer, not finite or beyond the bound; column checksums that differ; row
+ * checksums that differ (a probe adds the three into "abftMismatches"). nfaults > 0: after that run,
+ * for each i the element fault_index[i] (row * n + col) of the device C is set to fault_value[i], the
+ * sequence runs again, the element is put back; fault_counts[3 i ..] are that run's three counts.
+ *
+ * gemm_ref: the VALU reference of the element check, R[m][n] (fp32) = A * Bt^T, same contract.
+ * count_diff: the element check's comparer with its production grid: how many of the count
+ * (1 .. 2^31) elements of x and y differ.
+ *
+ * gen_operands: the in-probe operand generator with its production grid into buffers that start
+ * as 0xFF bytes. bf16: count elements of small_int(seed, span = span_or_scale_lo in 1..127) into
+ * operand (>= 2 count bytes), and the first nzero words of zero (may be NULL with nzero 0) zeroed;
+ * scales NULL. Low precision: count elements (whole 32-bit words) into operand, count / 32 E8M0
+ * bytes 2^scale_lo | 2^(scale_lo + 1) into scales for the scaled dtypes (NULL for fp8); nzero 0 and
+ * zero NULL. The whole of every buffer (its *_bytes) comes back, so what the generator must not
+ * touch still holds 0xFF. */
+int mi355x_probe_abft_check(int device, int dtype, const void* A, const void* Bt, const void* scaleA,
+                            const void* scaleBt, const void* C, int m, int n, int k, float bound,
+                            unsigned int* vectors, unsigned long long* counts, int nfaults,
+                            const long long* fault_index, const float* fault_value,
+                            unsigned long long* fault_counts);
+int mi355x_probe_gemm_ref(int device, int dtype, const void* A, const void* Bt, const void* scaleA,
+                          const void* scaleBt, void* R, int m, int n, int k);
+int mi355x_probe_count_diff(int device, const float* x, const float* y, unsigned long long count,
+                            unsigned long long* bad);
+int mi355x_probe_gen_operands(int device, int dtype, unsigned int seed, int span_or_scale_lo,
+                              unsigned long long count, unsigned long long nzero, void* operand,
+                              size_t operand_bytes, void* scales, size_t scale_bytes, void* zero,
+                              size_t zero_bytes);
 void mi355x_probe_free(char* p);
 
 #ifdef __cplusplus

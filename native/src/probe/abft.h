@@ -50,14 +50,25 @@ __global__ void gemm_ref_valu(const short* __restrict__ A, const short* __restri
   C[static_cast<int64_t>(m) * N + n] = s;
 }
 
+// Bit-exact: the words are compared, so a zero of the other sign differs and a NaN equals the NaN
+// of the same bits.
 __global__ void count_diff(const float* __restrict__ x, const float* __restrict__ y, uint64_t n,
                            unsigned long long* __restrict__ bad) {
   uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   uint32_t b = 0;
-  for (; i < n; i += static_cast<uint64_t>(gridDim.x) * blockDim.x) b += x[i] != y[i];
+  for (; i < n; i += static_cast<uint64_t>(gridDim.x) * blockDim.x) b += __float_as_uint(x[i]) != __float_as_uint(y[i]);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) b += __shfl_xor(b, off, 64);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(bad, static_cast<unsigned long long>(b));
+}
+
+// The element check's two launches, as the probe and the host-buffer test surfaces share them: the
+// reference of C[m][n] = A[m][k] * Bt[n][k]^T (k % 8 == 0), and count_diff with its one grid.
+inline void launch_gemm_ref(hipStream_t s, const short* a, const short* bt, float* r, int m, int n, int k) {
+  hipLaunchKernelGGL(gemm_ref_valu, dim3((n + 255) / 256, m), dim3(256), 0, s, a, bt, r, m, n, k);
+}
+inline void launch_count_diff(hipStream_t s, const float* x, const float* y, uint64_t count, unsigned long long* bad) {
+  hipLaunchKernelGGL(count_diff, dim3(64), dim3(256), 0, s, x, y, count, bad);
 }
 
 // ABFT (algorithm-based fault tolerance) checks. Every operand is a small integer, so with
@@ -70,8 +81,10 @@ __global__ void count_diff(const float* __restrict__ x, const float* __restrict_
 // GEMM they check).
 __device__ __forceinline__ uint32_t to_u32(short v) { return static_cast<uint32_t>(static_cast<int>(bf16_to_f32(v))); }
 __device__ __forceinline__ uint32_t to_u32(float v) {
-  // clamp first: an out-of-range float-to-int conversion is undefined (colsum_partial flags it)
-  return static_cast<uint32_t>(static_cast<int>(fminf(fmaxf(v, -2.0e9f), 2.0e9f)));
+  // clamp first: an out-of-range float-to-int conversion is undefined (colsum_partial flags it).
+  // Rounded down, not towards zero: an element that gained a fraction keeps its integer part
+  // whatever its sign, so it is the integrality flag alone that reports it.
+  return static_cast<uint32_t>(static_cast<int>(floorf(fminf(fmaxf(v, -2.0e9f), 2.0e9f))));
 }
 
 constexpr int kColRows = 64;  // rows per colsum_partial block (4 waves x 16 interleaved rows)
@@ -174,6 +187,9 @@ __global__ void inject_gemm_fault(float* __restrict__ c, int64_t idx, int mode) 
   else c[idx] = __int_as_float(0x7fc00000);
 }
 
+// test surface (mi355x_probe_abft_check): one element of C set to a value the host chose
+__global__ void poke_f32(float* __restrict__ c, int64_t idx, float v) { c[idx] = v; }
+
 __global__ void count_ne_u32(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, int n,
                              unsigned long long* __restrict__ bad) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -181,6 +197,55 @@ __global__ void count_ne_u32(const uint32_t* __restrict__ a, const uint32_t* __r
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
   if ((threadIdx.x & 63) == 0 && d) atomicAdd(bad, static_cast<unsigned long long>(d));
+}
+
+// The six checksum vectors of one C[m][n] = A[m][k] * Bt[n][k]^T, of K, K, N, N, M and M words:
+// column sums of A and of Bt, column sums of C and what they must be, row sums of C and what they
+// must be. Each at least 32-byte aligned (rowdot<short> loads eight weights at once). The first
+// three accumulate atomically: the caller zeroes them on the stream first.
+struct AbftVectors {
+  uint32_t *acol, *bcol, *col_c, *exp_col, *row_c, *exp_row;
+};
+// Where the checks count: elements of C that are no integer, not finite or beyond the bound; column
+// checksums that differ; row checksums that differ. A probe points all three at its one ABFT slot.
+struct AbftCounters {
+  unsigned long long *odd, *col, *row;
+};
+
+// The checks on C that read no operand, shared by the bf16 and the low-precision sequence: the
+// column sums with the integrality / range flag, and the row sums.
+inline void enqueue_abft_c_colsum(hipStream_t s, const float* c, int m, int n, float bound, const AbftVectors& v,
+                                  const AbftCounters& cnt) {
+  const dim3 grid((n + 255) / 256, (m + kColRows - 1) / kColRows);
+  hipLaunchKernelGGL(colsum_partial<float>, grid, dim3(256), 0, s, c, m, n, v.col_c, bound, cnt.odd);
+}
+inline void enqueue_abft_c_rowsum(hipStream_t s, const float* c, int m, int n, const AbftVectors& v) {
+  hipLaunchKernelGGL(rowdot<float>, dim3((m + 3) / 4), dim3(256), 0, s, c, m, n, static_cast<const uint32_t*>(nullptr),
+                     v.row_c);
+}
+inline void enqueue_abft_compare(hipStream_t s, int m, int n, const AbftVectors& v, const AbftCounters& cnt) {
+  hipLaunchKernelGGL(count_ne_u32, dim3((n + 255) / 256), dim3(256), 0, s, static_cast<const uint32_t*>(v.col_c),
+                     static_cast<const uint32_t*>(v.exp_col), n, cnt.col);
+  hipLaunchKernelGGL(count_ne_u32, dim3((m + 255) / 256), dim3(256), 0, s, static_cast<const uint32_t*>(v.row_c),
+                     static_cast<const uint32_t*>(v.exp_row), m, cnt.row);
+}
+
+// The bf16 checker sequence on stream s (no host sync): A [m][k], Bt [n][k] bf16 small integers,
+// C [m][n] fp32; k % 8 == 0, n % 4 == 0. bound: the largest |C| the operands allow.
+inline void enqueue_abft(hipStream_t s, const short* a, const short* bt, const float* c, int m, int n, int k, float bound,
+                         const AbftVectors& v, const AbftCounters& cnt) {
+  const dim3 agrid((k + 511) / 512, (m + kColRows - 1) / kColRows), bgrid((k + 511) / 512, (n + kColRows - 1) / kColRows);
+  hipLaunchKernelGGL(colsum_partial<short>, agrid, dim3(256), 0, s, a, m, k, v.acol, 0.f,
+                     static_cast<unsigned long long*>(nullptr));
+  hipLaunchKernelGGL(colsum_partial<short>, bgrid, dim3(256), 0, s, bt, n, k, v.bcol, 0.f,
+                     static_cast<unsigned long long*>(nullptr));
+  enqueue_abft_c_colsum(s, c, m, n, bound, v, cnt);
+  hipLaunchKernelGGL(rowdot<short>, dim3((n + 3) / 4), dim3(256), 0, s, bt, n, k, static_cast<const uint32_t*>(v.acol),
+                     v.exp_col);
+  enqueue_abft_c_rowsum(s, c, m, n, v);
+  hipLaunchKernelGGL(rowdot<short>, dim3((m + 3) / 4), dim3(256), 0, s, a, m, k, static_cast<const uint32_t*>(v.bcol),
+                     v.exp_row);
+  enqueue_abft_compare(s, m, n, v, cnt);
 }
 
 }  // namespace

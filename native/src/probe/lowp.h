@@ -435,6 +435,33 @@ __global__ __launch_bounds__(256) void rowdot(const uint8_t* __restrict__ X, con
 
 __global__ void inject_fault(float* __restrict__ c, int64_t idx) { c[idx] += 1.0f; }  // test hook
 
+// The element check's reference launch, as the probe and the host-buffer test surface share it
+// (k % 32 == 0); its count_diff is abft.h's launch_count_diff.
+template <class T>
+void launch_gemm_ref(hipStream_t s, const uint8_t* a, const uint8_t* bt, const uint8_t* sa, const uint8_t* sb, float* r, int m,
+                     int n, int k) {
+  hipLaunchKernelGGL(gemm_ref<T>, dim3((n + 255) / 256, m), dim3(256), 0, s, a, bt, sa, sb, r, m, n, k);
+}
+
+// The low-precision checker sequence on stream s (no host sync), abft.h's enqueue_abft over the
+// decoded, scaled operands: A [m][k], Bt [n][k] elements of T with their scales (null: unscaled),
+// C [m][n] fp32; k % 32 == 0, n % 4 == 0. The caller zeroes the first three vectors on s first.
+template <class T>
+void enqueue_abft(hipStream_t s, const uint8_t* a, const uint8_t* bt, const uint8_t* sa, const uint8_t* sb, const float* c,
+                  int m, int n, int k, float bound, const AbftVectors& v, const AbftCounters& cnt) {
+  constexpr int E = 32 / T::kBits;
+  const int xblocks = (k / E + 255) / 256;
+  hipLaunchKernelGGL(colsum<T>, dim3(xblocks, (m + kColSlab - 1) / kColSlab), dim3(256), 0, s, a, sa, m, k, v.acol);
+  hipLaunchKernelGGL(colsum<T>, dim3(xblocks, (n + kColSlab - 1) / kColSlab), dim3(256), 0, s, bt, sb, n, k, v.bcol);
+  enqueue_abft_c_colsum(s, c, m, n, bound, v, cnt);
+  hipLaunchKernelGGL(rowdot<T>, dim3((n + 3) / 4), dim3(256), 0, s, bt, sb, n, k, static_cast<const uint32_t*>(v.acol),
+                     v.exp_col);
+  enqueue_abft_c_rowsum(s, c, m, n, v);
+  hipLaunchKernelGGL(rowdot<T>, dim3((m + 3) / 4), dim3(256), 0, s, a, sa, m, k, static_cast<const uint32_t*>(v.bcol),
+                     v.exp_row);
+  enqueue_abft_compare(s, m, n, v, cnt);
+}
+
 // ------------------------------------------------------------------ host side: one dtype's phase
 // The dtype's counters (kSlot*) and the size of the region carved below (region_bytes): arena.h.
 constexpr int kCensusIters = 128;
@@ -444,7 +471,7 @@ constexpr int kCensusIters = 128;
 // the caller on s. gemm_n: a multiple of 128.
 template <class T>
 void launch_phase_t(hipStream_t s, int dtype, char* region, int gemm_n, int cus, unsigned long long* cnt,
-                         hipEvent_t e0, hipEvent_t e1, bool inject, int census_fault_xcc, bool poison_c) {
+                         hipEvent_t e0, hipEvent_t e1, int64_t inject_at, int census_fault_xcc, bool poison_c) {
   const size_t n = static_cast<size_t>(gemm_n), n0 = kSmallN;
   char* p = region;
   auto carve = [&](size_t bytes) {
@@ -477,11 +504,8 @@ void launch_phase_t(hipStream_t s, int dtype, char* region, int gemm_n, int cus,
     hipLaunchKernelGGL(gen_operand<T>, dim3(64), dim3(256), 0, s, reinterpret_cast<uint32_t*>(b0), w0, sb0,
                        static_cast<uint64_t>(n0 * n0 / 32), seed ^ 0xBEEFu, scale_lo);
     launch_gemm(s, dtype, a0, b0, sa0, sb0, c0, in0, in0, in0);
-    hipLaunchKernelGGL(gemm_ref<T>, dim3(in0 / 256, in0), dim3(256), 0, s, static_cast<const uint8_t*>(a0),
-                       static_cast<const uint8_t*>(b0), static_cast<const uint8_t*>(sa0), static_cast<const uint8_t*>(sb0), r0,
-                       in0, in0, in0);
-    hipLaunchKernelGGL(count_diff, dim3(64), dim3(256), 0, s, static_cast<const float*>(c0), static_cast<const float*>(r0),
-                       static_cast<uint64_t>(n0 * n0), cnt + kSlotSmall);
+    launch_gemm_ref<T>(s, a0, b0, sa0, sb0, r0, in0, in0, in0);
+    launch_count_diff(s, c0, r0, static_cast<uint64_t>(n0 * n0), cnt + kSlotSmall);
     // (b) N^3, timed, exact ABFT
     hipLaunchKernelGGL(gen_operand<T>, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t*>(a), w, sa,
                        static_cast<uint64_t>(n * n / 32), seed ^ 0x51u, scale_lo);
@@ -490,25 +514,10 @@ void launch_phase_t(hipStream_t s, int dtype, char* region, int gemm_n, int cus,
     PROBE_CHECK(hipEventRecord(e0, s));
     launch_gemm(s, dtype, a, b, sa, sb, c, gemm_n, gemm_n, gemm_n);
     PROBE_CHECK(hipEventRecord(e1, s));
-    if (inject)
-      hipLaunchKernelGGL(inject_fault, dim3(1), dim3(1), 0, s, c, static_cast<int64_t>(gemm_n / 3) * gemm_n + gemm_n / 5);
-    constexpr int E = 32 / T::kBits;
-    const dim3 cgrid((gemm_n / E + 255) / 256, (gemm_n + kColSlab - 1) / kColSlab);
-    const dim3 cgrid_f((gemm_n + 255) / 256, (gemm_n + kColRows - 1) / kColRows), rgrid((gemm_n + 3) / 4);
-    hipLaunchKernelGGL(colsum<T>, cgrid, dim3(256), 0, s, static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(sa),
-                       gemm_n, gemm_n, vacol);
-    hipLaunchKernelGGL(colsum<T>, cgrid, dim3(256), 0, s, static_cast<const uint8_t*>(b), static_cast<const uint8_t*>(sb),
-                       gemm_n, gemm_n, vbcol);
-    hipLaunchKernelGGL(colsum_partial<float>, cgrid_f, dim3(256), 0, s, static_cast<const float*>(c), gemm_n, gemm_n, vcolC,
-                       bound, cnt + kSlotAbft);
-    hipLaunchKernelGGL(rowdot<T>, rgrid, dim3(256), 0, s, static_cast<const uint8_t*>(b), static_cast<const uint8_t*>(sb),
-                       gemm_n, gemm_n, static_cast<const uint32_t*>(vacol), vexpC);
-    hipLaunchKernelGGL(::rowdot<float>, rgrid, dim3(256), 0, s, static_cast<const float*>(c), gemm_n, gemm_n,
-                       static_cast<const uint32_t*>(nullptr), vrowC);
-    hipLaunchKernelGGL(rowdot<T>, rgrid, dim3(256), 0, s, static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(sa),
-                       gemm_n, gemm_n, static_cast<const uint32_t*>(vbcol), vexpR);
-    hipLaunchKernelGGL(count_ne_u32, dim3((gemm_n + 255) / 256), dim3(256), 0, s, vcolC, vexpC, gemm_n, cnt + kSlotAbft);
-    hipLaunchKernelGGL(count_ne_u32, dim3((gemm_n + 255) / 256), dim3(256), 0, s, vrowC, vexpR, gemm_n, cnt + kSlotAbft);
+    if (inject_at >= 0) hipLaunchKernelGGL(inject_fault, dim3(1), dim3(1), 0, s, c, inject_at);
+    unsigned long long* bad = cnt + kSlotAbft;
+    enqueue_abft<T>(s, a, b, sa, sb, c, gemm_n, gemm_n, gemm_n, bound, AbftVectors{vacol, vbcol, vcolC, vexpC, vrowC, vexpR},
+                    AbftCounters{bad, bad, bad});
     // (c) every CU on this dtype's instruction
     hipLaunchKernelGGL(census<T>, dim3(8 * cus), dim3(kCensusThreads), 0, s, cnt + kSlotCensusMap, cnt + kSlotCensusBad,
                        kCensusIters, 0xC0FFEEu ^ static_cast<uint32_t>(gemm_n) ^ (static_cast<uint32_t>(dtype) << 20),
@@ -517,10 +526,10 @@ void launch_phase_t(hipStream_t s, int dtype, char* region, int gemm_n, int cus,
 }
 
 inline void launch_phase(hipStream_t s, int dtype, char* region, int gemm_n, int cus, unsigned long long* cnt,
-                         hipEvent_t e0, hipEvent_t e1, bool inject, int census_fault_xcc, bool poison_c) {
-  if (dtype == kFp8) launch_phase_t<Fp8>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject, census_fault_xcc, poison_c);
-  else if (dtype == kMxFp8) launch_phase_t<MxFp8>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject, census_fault_xcc, poison_c);
-  else launch_phase_t<MxFp4>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject, census_fault_xcc, poison_c);
+                         hipEvent_t e0, hipEvent_t e1, int64_t inject_at, int census_fault_xcc, bool poison_c) {
+  if (dtype == kFp8) launch_phase_t<Fp8>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject_at, census_fault_xcc, poison_c);
+  else if (dtype == kMxFp8) launch_phase_t<MxFp8>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject_at, census_fault_xcc, poison_c);
+  else launch_phase_t<MxFp4>(s, dtype, region, gemm_n, cus, cnt, e0, e1, inject_at, census_fault_xcc, poison_c);
 }
 
 // What the phase needs of a probe: where its memory and events are, and the options.
@@ -532,6 +541,7 @@ struct Phase {
   hipEvent_t (*ev)[2] = nullptr;        // per dtype: around the timed GEMM
   int gemm_n = 0, cus = 0;
   int inject_mask = 0, census_fault_xcc = -1;  // test hooks
+  int64_t inject_at = -1;                      // the element inject_mask's dtypes corrupt; -1: none
   bool poison_c = false;
 };
 
@@ -543,7 +553,7 @@ inline void launch(hipStream_t s, const Phase& ph) {
   for (int d = 0; d < kDtypes; ++d)
     if (ph.mask >> d & 1)
       launch_phase(s, d, ph.region, ph.gemm_n, ph.cus, ph.cnt + d * kSlots, ph.ev[d][0], ph.ev[d][1],
-                   (ph.inject_mask >> d & 1) != 0, ph.census_fault_xcc, ph.poison_c);
+                   (ph.inject_mask >> d & 1) ? ph.inject_at : -1, ph.census_fault_xcc, ph.poison_c);
   PROBE_CHECK(hipGetLastError());
   PROBE_CHECK(hipMemcpyAsync(ph.host, ph.cnt, kDtypes * kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 }

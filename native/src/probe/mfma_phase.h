@@ -65,10 +65,8 @@ inline void enqueue_element_check(const MfmaPhase& ph) {
                      zero_mfma ? static_cast<uint64_t>(kResSlots - kSlotSmall) * 2 : 0);
   hipLaunchKernelGGL(gen_operand, dim3(256), dim3(256), 0, s, b0, e0, 0xBEEFu, 3, static_cast<uint32_t*>(nullptr), 0);
   ph.gemm(a0, b0, c0, static_cast<int>(n0), nullptr);
-  hipLaunchKernelGGL(gemm_ref_valu, dim3(n0 / 256, n0), dim3(256), 0, s, a0, b0, r0, static_cast<int>(n0),
-                     static_cast<int>(n0), static_cast<int>(n0));
-  hipLaunchKernelGGL(count_diff, dim3(64), dim3(256), 0, s, static_cast<const float*>(c0), static_cast<const float*>(r0),
-                     e0, cnt + kSlotSmall);
+  launch_gemm_ref(s, a0, b0, r0, static_cast<int>(n0), static_cast<int>(n0), static_cast<int>(n0));
+  launch_count_diff(s, c0, r0, e0, cnt + kSlotSmall);
   PROBE_CHECK(hipGetLastError());
 }
 
@@ -97,9 +95,8 @@ inline void enqueue_timed_gemm(const MfmaPhase& ph, hipEvent_t ev0, hipEvent_t e
   for (int rep = 0; rep < o.reps; ++rep) ph.gemm(a, b, c, gemm_n, cnt + kSlotGemmMap);  // reps 0: test hook
   PROBE_CHECK(hipEventRecord(ev1, s));
   PROBE_CHECK(hipGetLastError());
-  if (o.inject_gemm)
-    hipLaunchKernelGGL(inject_gemm_fault, dim3(1), dim3(1), 0, s, c, static_cast<int64_t>(gemm_n / 3) * gemm_n + gemm_n / 5,
-                       o.inject_gemm);
+  const int64_t at = o.inject_gemm_at.index(gemm_n);
+  if (o.inject_gemm && at >= 0) hipLaunchKernelGGL(inject_gemm_fault, dim3(1), dim3(1), 0, s, c, at, o.inject_gemm);
 }
 
 // ...and its exact u32 (mod 2^32) ABFT row / column checksums
@@ -115,24 +112,10 @@ inline void enqueue_abft(const MfmaPhase& ph) {
   uint32_t *vacol = v32, *vbcol = v32 + n, *vcolC = v32 + 2 * n, *vexpC = v32 + 3 * n, *vrowC = v32 + 4 * n,
            *vexpR = v32 + 5 * n;
   if (!zero_mfma) PROBE_CHECK(hipMemsetAsync(v32, 0, 3 * n * sizeof(uint32_t), s));
-  const int rows_y = (gemm_n + kColRows - 1) / kColRows;
-  const dim3 cgrid_h((gemm_n + 511) / 512, rows_y), cgrid_f((gemm_n + 255) / 256, rows_y);
   const float bound = static_cast<float>(gemm_n) * 4.0f;  // |C| <= K * span^2, span 2
-  hipLaunchKernelGGL(colsum_partial<short>, cgrid_h, dim3(256), 0, s, static_cast<const short*>(a), gemm_n, gemm_n, vacol,
-                     0.f, static_cast<unsigned long long*>(nullptr));
-  hipLaunchKernelGGL(colsum_partial<short>, cgrid_h, dim3(256), 0, s, static_cast<const short*>(b), gemm_n, gemm_n, vbcol,
-                     0.f, static_cast<unsigned long long*>(nullptr));
-  hipLaunchKernelGGL(colsum_partial<float>, cgrid_f, dim3(256), 0, s, static_cast<const float*>(c), gemm_n, gemm_n, vcolC,
-                     bound, cnt + kSlotAbft);
-  const dim3 rgrid((gemm_n + 3) / 4);
-  hipLaunchKernelGGL(rowdot<short>, rgrid, dim3(256), 0, s, static_cast<const short*>(b), gemm_n, gemm_n,
-                     static_cast<const uint32_t*>(vacol), vexpC);
-  hipLaunchKernelGGL(rowdot<float>, rgrid, dim3(256), 0, s, static_cast<const float*>(c), gemm_n, gemm_n,
-                     static_cast<const uint32_t*>(nullptr), vrowC);
-  hipLaunchKernelGGL(rowdot<short>, rgrid, dim3(256), 0, s, static_cast<const short*>(a), gemm_n, gemm_n,
-                     static_cast<const uint32_t*>(vbcol), vexpR);
-  hipLaunchKernelGGL(count_ne_u32, dim3((gemm_n + 255) / 256), dim3(256), 0, s, vcolC, vexpC, gemm_n, cnt + kSlotAbft);
-  hipLaunchKernelGGL(count_ne_u32, dim3((gemm_n + 255) / 256), dim3(256), 0, s, vrowC, vexpR, gemm_n, cnt + kSlotAbft);
+  unsigned long long* bad = cnt + kSlotAbft;
+  enqueue_abft(s, a, b, c, gemm_n, gemm_n, gemm_n, bound, AbftVectors{vacol, vbcol, vcolC, vexpC, vrowC, vexpR},
+               AbftCounters{bad, bad, bad});
 }
 
 // Enqueues the whole MFMA phase on stream s (no host sync): (a) a 256^3 GEMM checked element by

@@ -143,6 +143,19 @@ struct Plan {
 
 }  // namespace hostlink
 
+// Where the GEMM fault hooks corrupt C (test hooks "injectGemmFaultRow" / "injectGemmFaultCol"):
+// -1 is the element the hooks always took, row n/3 and column n/5; any other value outside [0, n)
+// means no fault, like "injectFlipAtChunk".
+struct FaultAt {
+  long long row = -1, col = -1;
+  // the element's index in an n x n C, or -1: no fault
+  long long index(int n) const {
+    const long long r = row == -1 ? n / 3 : row, c = col == -1 ? n / 5 : col;
+    if (r < 0 || r >= n || c < 0 || c >= n) return -1;
+    return r * n + c;
+  }
+};
+
 // Every option of mi355x_probe_run.
 struct ProbeOptions {
   uint64_t hbm_bytes = 1ull << 30;
@@ -158,6 +171,7 @@ struct ProbeOptions {
   GemmOptions gemm;               // variant.tile is 256 or 128 here
   int reps = 1;                   // 0 with "gemmSkip" (test hook, with poisonC): C keeps the poison
   int inject_gemm = 0;            // test hook
+  FaultAt inject_gemm_at;         // test hook: where injectGemmFault and injectLowpFault strike
   int census_fault_xcc = -1;      // test hook
   bool require_all_cus = true;
   bool cu_keys = false;
@@ -201,6 +215,8 @@ struct ProbeOptions {
     o.gemm.variant.tile = o.gemm.variant.tile != 128 ? 256 : 128;
     o.reps = opt_int(json, "gemmSkip", 0) ? 0 : static_cast<int>(std::max(1LL, opt_int(json, "gemmReps", 1)));
     o.inject_gemm = static_cast<int>(opt_int(json, "injectGemmFault", 0));
+    o.inject_gemm_at.row = opt_int(json, "injectGemmFaultRow", -1);
+    o.inject_gemm_at.col = opt_int(json, "injectGemmFaultCol", -1);
     o.census_fault_xcc = static_cast<int>(opt_int(json, "injectCensusFaultXcc", -1));
     o.require_all_cus = opt_bool(json, "requireAllCUs", true);
     o.cu_keys = opt_bool(json, "cuKeys", false);

@@ -128,6 +128,7 @@ lowp::Phase lowp_phase(DeviceCtx& ctx, const ProbeOptions& o, char* base, const 
   lp.gemm_n = o.gemm_n;
   lp.cus = ctx.prop.multiProcessorCount;
   lp.inject_mask = o.inject_lowp;
+  lp.inject_at = o.inject_gemm_at.index(o.gemm_n);
   lp.census_fault_xcc = o.lowp_census_fault_xcc;
   lp.poison_c = o.gemm.poison_c;
   return lp;
@@ -296,6 +297,67 @@ void gemm_on_host_buffers(int dev, std::vector<HostOperand> in, void* C, size_t 
   launch(d);
   PROBE_CHECK(hipGetLastError());
   PROBE_CHECK(hipMemcpy(C, dc.p, c_bytes, hipMemcpyDeviceToHost));
+}
+
+// ------------------------------------------------------------------ the checkers on host buffers (test surfaces)
+constexpr int kBf16 = -1;           // the dtype argument of these entry points: bf16, else a lowp::Dtype
+constexpr int kMaxCheckDim = 65535;  // m, n, k: the reference's grid has one row of blocks per m
+
+// The contract of mi355x_probe_abft_check and mi355x_probe_gemm_ref.
+bool checker_args_ok(int dtype, const void* A, const void* Bt, const void* sA, const void* sB, int m, int n, int k) {
+  if (!A || !Bt || m < 1 || n < 1 || k < 1 || m > kMaxCheckDim || n > kMaxCheckDim || k > kMaxCheckDim || n % 4) return false;
+  if (dtype == kBf16) return k % 8 == 0 && !sA && !sB;
+  if (dtype < 0 || dtype >= lowp::kDtypes || k % 32) return false;
+  return lowp::scaled(dtype) ? (sA && sB) : (!sA && !sB);
+}
+
+size_t operand_row_bytes(int dtype, int k) {
+  return dtype == kBf16 ? static_cast<size_t>(k) * 2 : static_cast<size_t>(k) * lowp::bits_of(dtype) / 8;
+}
+
+// A device copy of ``bytes`` of host memory; a null host pointer leaves the buffer null.
+void upload(DevBuf& d, const void* host, size_t bytes) {
+  if (!host) return;
+  PROBE_CHECK(hipMalloc(&d.p, bytes));
+  PROBE_CHECK(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+}
+
+// The production checker sequence of ``dtype`` (mfma_phase.h's enqueue_abft, lowp::enqueue_abft).
+void enqueue_checkers(hipStream_t s, int dtype, const void* a, const void* bt, const void* sa, const void* sb, const float* c,
+                      int m, int n, int k, float bound, const AbftVectors& v, const AbftCounters& cnt) {
+  auto u8 = [](const void* p) { return static_cast<const uint8_t*>(p); };
+  if (dtype == kBf16)
+    enqueue_abft(s, static_cast<const short*>(a), static_cast<const short*>(bt), c, m, n, k, bound, v, cnt);
+  else if (dtype == lowp::kFp8)
+    lowp::enqueue_abft<lowp::Fp8>(s, u8(a), u8(bt), u8(sa), u8(sb), c, m, n, k, bound, v, cnt);
+  else if (dtype == lowp::kMxFp8)
+    lowp::enqueue_abft<lowp::MxFp8>(s, u8(a), u8(bt), u8(sa), u8(sb), c, m, n, k, bound, v, cnt);
+  else
+    lowp::enqueue_abft<lowp::MxFp4>(s, u8(a), u8(bt), u8(sa), u8(sb), c, m, n, k, bound, v, cnt);
+}
+
+void launch_reference(hipStream_t s, int dtype, const void* a, const void* bt, const void* sa, const void* sb, float* r, int m,
+                      int n, int k) {
+  auto u8 = [](const void* p) { return static_cast<const uint8_t*>(p); };
+  if (dtype == kBf16) launch_gemm_ref(s, static_cast<const short*>(a), static_cast<const short*>(bt), r, m, n, k);
+  else if (dtype == lowp::kFp8) lowp::launch_gemm_ref<lowp::Fp8>(s, u8(a), u8(bt), u8(sa), u8(sb), r, m, n, k);
+  else if (dtype == lowp::kMxFp8) lowp::launch_gemm_ref<lowp::MxFp8>(s, u8(a), u8(bt), u8(sa), u8(sb), r, m, n, k);
+  else lowp::launch_gemm_ref<lowp::MxFp4>(s, u8(a), u8(bt), u8(sa), u8(sb), r, m, n, k);
+}
+
+// The production operand generator of ``dtype`` with its production grid.
+void launch_generator(hipStream_t s, int dtype, void* out, uint64_t count, uint8_t* scales, uint32_t seed, int arg,
+                      uint32_t* zero, uint64_t nzero) {
+  const dim3 grid(2048), block(256);
+  auto* words = static_cast<uint32_t*>(out);
+  if (dtype == kBf16)
+    hipLaunchKernelGGL(gen_operand, grid, block, 0, s, static_cast<short*>(out), count, seed, arg, zero, nzero);
+  else if (dtype == lowp::kFp8)
+    hipLaunchKernelGGL(lowp::gen_operand<lowp::Fp8>, grid, block, 0, s, words, count / 4, scales, count / 32, seed, arg);
+  else if (dtype == lowp::kMxFp8)
+    hipLaunchKernelGGL(lowp::gen_operand<lowp::MxFp8>, grid, block, 0, s, words, count / 4, scales, count / 32, seed, arg);
+  else
+    hipLaunchKernelGGL(lowp::gen_operand<lowp::MxFp4>, grid, block, 0, s, words, count / 8, scales, count / 32, seed, arg);
 }
 
 }  // namespace
@@ -474,6 +536,142 @@ int mi355x_probe_gemm_lowp(int dev, int dtype, const void* A, const void* Bt, co
                                              static_cast<const uint8_t*>(d[1].p), static_cast<const uint8_t*>(d[2].p),
                                              static_cast<const uint8_t*>(d[3].p), static_cast<float*>(d[4].p), m, n, k);
                          });
+  });
+}
+
+int mi355x_probe_abft_check(int dev, int dtype, const void* A, const void* Bt, const void* scaleA, const void* scaleBt,
+                            const void* C, int m, int n, int k, float bound, unsigned int* vectors,
+                            unsigned long long* counts, int nfaults, const long long* fault_index, const float* fault_value,
+                            unsigned long long* fault_counts) {
+  if (!device_ok(dev)) return -1;
+  if (!C || !vectors || !counts || !checker_args_ok(dtype, A, Bt, scaleA, scaleBt, m, n, k)) return -2;
+  if (nfaults < 0 || (nfaults > 0 && (!fault_index || !fault_value || !fault_counts))) return -2;
+  const long long elems = static_cast<long long>(m) * n;
+  for (int i = 0; i < nfaults; ++i)
+    if (fault_index[i] < 0 || fault_index[i] >= elems) return -2;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded_status([&] {
+    PROBE_CHECK(hipSetDevice(dev));
+    const size_t kb = operand_row_bytes(dtype, k), ks = static_cast<size_t>(k) / 32;
+    DevBuf da, db, dsa, dsb, dc, dv, dcnt;
+    upload(da, A, m * kb);
+    upload(db, Bt, n * kb);
+    upload(dsa, scaleA, m * ks);
+    upload(dsb, scaleBt, n * ks);
+    upload(dc, C, static_cast<size_t>(elems) * 4);
+    // the six vectors, each from a 32-byte boundary; the three that accumulate come first
+    auto pad8 = [](size_t words) { return (words + 7) & ~static_cast<size_t>(7); };
+    const size_t pk = pad8(k), pn = pad8(n), pm = pad8(m), vwords = 2 * pk + 2 * pn + 2 * pm;
+    PROBE_CHECK(hipMalloc(&dv.p, vwords * 4));
+    auto* v32 = static_cast<uint32_t*>(dv.p);
+    const AbftVectors v{v32, v32 + pk, v32 + 2 * pk, v32 + 2 * pk + pn, v32 + 2 * pk + 2 * pn, v32 + 2 * pk + 2 * pn + pm};
+    const size_t runs = static_cast<size_t>(nfaults) + 1;
+    PROBE_CHECK(hipMalloc(&dcnt.p, runs * 3 * sizeof(unsigned long long)));
+    PROBE_CHECK(hipMemset(dcnt.p, 0, runs * 3 * sizeof(unsigned long long)));
+    auto* cnt = static_cast<unsigned long long*>(dcnt.p);
+    auto* c = static_cast<float*>(dc.p);
+    auto check = [&](size_t run) {
+      PROBE_CHECK(hipMemsetAsync(v32, 0, (2 * pk + pn) * 4, nullptr));
+      enqueue_checkers(nullptr, dtype, da.p, db.p, dsa.p, dsb.p, c, m, n, k, bound, v,
+                       AbftCounters{cnt + 3 * run, cnt + 3 * run + 1, cnt + 3 * run + 2});
+      PROBE_CHECK(hipGetLastError());
+    };
+    check(0);
+    std::vector<uint32_t> hv(vwords);
+    PROBE_CHECK(hipMemcpy(hv.data(), v32, vwords * 4, hipMemcpyDeviceToHost));
+    // one fault at a time: the element set, the sequence run, the element put back
+    const float* hc = static_cast<const float*>(C);
+    for (int i = 0; i < nfaults; ++i) {
+      hipLaunchKernelGGL(poke_f32, dim3(1), dim3(1), 0, nullptr, c, static_cast<int64_t>(fault_index[i]), fault_value[i]);
+      check(static_cast<size_t>(i) + 1);
+      hipLaunchKernelGGL(poke_f32, dim3(1), dim3(1), 0, nullptr, c, static_cast<int64_t>(fault_index[i]), hc[fault_index[i]]);
+    }
+    std::vector<unsigned long long> hcnt(runs * 3);
+    PROBE_CHECK(hipMemcpy(hcnt.data(), cnt, hcnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    // packed for the caller: K, K, N, N, M, M words
+    const size_t from[6] = {0, pk, 2 * pk, 2 * pk + pn, 2 * pk + 2 * pn, 2 * pk + 2 * pn + pm};
+    const size_t len[6] = {static_cast<size_t>(k), static_cast<size_t>(k), static_cast<size_t>(n),
+                           static_cast<size_t>(n), static_cast<size_t>(m), static_cast<size_t>(m)};
+    unsigned int* out = vectors;
+    for (int i = 0; i < 6; ++i) {
+      std::memcpy(out, hv.data() + from[i], len[i] * 4);
+      out += len[i];
+    }
+    std::memcpy(counts, hcnt.data(), 3 * sizeof(unsigned long long));
+    if (nfaults) std::memcpy(fault_counts, hcnt.data() + 3, static_cast<size_t>(nfaults) * 3 * sizeof(unsigned long long));
+  });
+}
+
+int mi355x_probe_gemm_ref(int dev, int dtype, const void* A, const void* Bt, const void* scaleA, const void* scaleBt,
+                          void* R, int m, int n, int k) {
+  if (!device_ok(dev)) return -1;
+  if (!R || !checker_args_ok(dtype, A, Bt, scaleA, scaleBt, m, n, k)) return -2;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded_status([&] {
+    const size_t kb = operand_row_bytes(dtype, k), ks = static_cast<size_t>(k) / 32;
+    // the device R starts as 0xFF bytes: an element the reference never writes comes back as NaN
+    gemm_on_host_buffers(dev, {{A, m * kb}, {Bt, n * kb}, {scaleA, m * ks}, {scaleBt, n * ks}}, R,
+                         static_cast<size_t>(m) * n * 4, true, [&](std::vector<DevBuf>& d) {
+                           launch_reference(nullptr, dtype, d[0].p, d[1].p, d[2].p, d[3].p, static_cast<float*>(d[4].p), m, n, k);
+                         });
+  });
+}
+
+int mi355x_probe_count_diff(int dev, const float* x, const float* y, unsigned long long count, unsigned long long* bad) {
+  if (!device_ok(dev)) return -1;
+  if (!x || !y || !bad || count < 1 || count > (1ull << 31)) return -2;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded_status([&] {
+    PROBE_CHECK(hipSetDevice(dev));
+    DevBuf dx, dy, dbad;
+    upload(dx, x, count * 4);
+    upload(dy, y, count * 4);
+    PROBE_CHECK(hipMalloc(&dbad.p, sizeof(unsigned long long)));
+    PROBE_CHECK(hipMemset(dbad.p, 0, sizeof(unsigned long long)));
+    launch_count_diff(nullptr, static_cast<const float*>(dx.p), static_cast<const float*>(dy.p), count,
+                      static_cast<unsigned long long*>(dbad.p));
+    PROBE_CHECK(hipGetLastError());
+    unsigned long long h = 0;
+    PROBE_CHECK(hipMemcpy(&h, dbad.p, sizeof h, hipMemcpyDeviceToHost));
+    *bad = h;
+  });
+}
+
+int mi355x_probe_gen_operands(int dev, int dtype, unsigned int seed, int span_or_scale_lo, unsigned long long count,
+                              unsigned long long nzero, void* operand, size_t operand_bytes, void* scales,
+                              size_t scale_bytes, void* zero, size_t zero_bytes) {
+  if (!device_ok(dev)) return -1;
+  if (!operand || count < 1 || count > (1ull << 31) || nzero > (1ull << 28)) return -2;
+  if (dtype != kBf16 && (dtype < 0 || dtype >= lowp::kDtypes)) return -2;
+  const bool bf16 = dtype == kBf16, has_scales = !bf16 && lowp::scaled(dtype);
+  size_t need = 0;
+  if (bf16) {
+    if (span_or_scale_lo < 1 || span_or_scale_lo > 127) return -2;  // exact in bf16
+    need = count * 2;
+  } else {
+    // whole 32-bit words of elements, no zero region, scales that stay E8M0 powers of two
+    if (count % (32 / lowp::bits_of(dtype)) || nzero || zero || span_or_scale_lo < -126 || span_or_scale_lo > 126) return -2;
+    need = count * lowp::bits_of(dtype) / 8;
+  }
+  if (operand_bytes < need || (has_scales ? (!scales || scale_bytes < count / 32) : scales != nullptr)) return -2;
+  if (zero ? zero_bytes < nzero * 4 : nzero > 0) return -2;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded_status([&] {
+    PROBE_CHECK(hipSetDevice(dev));
+    DevBuf dop, dsc, dz;
+    auto filled = [](DevBuf& d, size_t bytes) {  // at least one byte, so an empty region is still a buffer
+      PROBE_CHECK(hipMalloc(&d.p, std::max<size_t>(bytes, 16)));
+      PROBE_CHECK(hipMemset(d.p, 0xFF, std::max<size_t>(bytes, 16)));
+    };
+    filled(dop, operand_bytes);
+    if (has_scales) filled(dsc, scale_bytes);
+    if (zero) filled(dz, zero_bytes);
+    launch_generator(nullptr, dtype, dop.p, count, static_cast<uint8_t*>(dsc.p), seed, span_or_scale_lo,
+                     static_cast<uint32_t*>(dz.p), nzero);
+    PROBE_CHECK(hipGetLastError());
+    PROBE_CHECK(hipMemcpy(operand, dop.p, operand_bytes, hipMemcpyDeviceToHost));
+    if (has_scales && scale_bytes) PROBE_CHECK(hipMemcpy(scales, dsc.p, scale_bytes, hipMemcpyDeviceToHost));
+    if (zero && zero_bytes) PROBE_CHECK(hipMemcpy(zero, dz.p, zero_bytes, hipMemcpyDeviceToHost));
   });
 }
 

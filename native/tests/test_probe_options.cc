@@ -28,6 +28,8 @@ static void expect_defaults(const ProbeOptions& o) {
   EXPECT_EQ(o.gemm.group_m, kGemmGroupM);
   EXPECT_EQ(o.reps, 1);
   EXPECT_EQ(o.inject_gemm, 0);
+  EXPECT_EQ(o.inject_gemm_at.row, -1LL);
+  EXPECT_EQ(o.inject_gemm_at.col, -1LL);
   EXPECT_EQ(o.census_fault_xcc, -1);
   EXPECT_TRUE(o.require_all_cus);
   EXPECT_TRUE(!o.cu_keys);
@@ -93,6 +95,25 @@ TEST(probe_options_low_precision_mask) {
   EXPECT_EQ(parse(R"({"mfmaLowPrecision":15})").lowp_mask, 7);
   EXPECT_EQ(parse(R"({"mfmaLowPrecision":5})").lowp_mask, 5);
   EXPECT_EQ(parse(R"({"mfma":false,"mfmaLowPrecision":7})").lowp_mask, 0);
+}
+
+TEST(probe_options_gemm_fault_position) {
+  const ProbeOptions d = parse(R"({"injectGemmFault":1})");
+  EXPECT_EQ(d.inject_gemm_at.row, -1LL);
+  EXPECT_EQ(d.inject_gemm_at.col, -1LL);
+  EXPECT_EQ(d.inject_gemm_at.index(512), 170LL * 512 + 102);  // n/3, n/5: where the hook always struck
+  EXPECT_EQ(d.inject_gemm_at.index(1024), 341LL * 1024 + 204);
+  const ProbeOptions at = parse(R"({"injectGemmFault":1,"injectGemmFaultRow":511,"injectGemmFaultCol":0})");
+  EXPECT_EQ(at.inject_gemm, 1);  // the longer keys are not the mode's key
+  EXPECT_EQ(at.inject_gemm_at.index(512), 511LL * 512);
+  EXPECT_EQ(at.inject_gemm_at.index(256), -1LL);  // row out of range: no fault
+  EXPECT_EQ(parse(R"({"injectGemmFaultRow":0,"injectGemmFaultCol":0})").inject_gemm_at.index(256), 0LL);
+  EXPECT_EQ(parse(R"({"injectGemmFaultRow":3})").inject_gemm_at.index(500), 3LL * 500 + 100);  // one default
+  EXPECT_EQ(parse(R"({"injectGemmFaultCol":512})").inject_gemm_at.index(512), -1LL);
+  EXPECT_EQ(parse(R"({"injectGemmFaultCol":-2})").inject_gemm_at.index(512), -1LL);
+  EXPECT_EQ(parse(R"({"injectGemmFaultRow":-7,"injectGemmFaultCol":5})").inject_gemm_at.index(512), -1LL);
+  EXPECT_EQ(parse(R"({"injectGemmFaultRow":65535,"injectGemmFaultCol":65535})").inject_gemm_at.index(65536),
+            65535LL * 65536 + 65535);  // no 32-bit wrap
 }
 
 TEST(probe_options_host_link) {
