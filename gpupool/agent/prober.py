@@ -239,6 +239,7 @@ class Prober:
         # spec.probe.hostLinkCheck: bytes of pinned host memory tested over PCIe (0 = off)
         hostlink = int(opts.get("hostLinkBytes") or schema.DEFAULT_HOST_LINK_BYTES) \
             if opts.get("hostLinkCheck") else 0
+        lds = bool(opts.get("ldsCheck"))  # spec.probe.ldsCheck: the per-CU LDS phase
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -256,6 +257,8 @@ class Prober:
                 args["lowPrecision"] = lowp
             if hostlink:
                 args["hostLinkBytes"] = hostlink
+            if lds:
+                args["ldsCheck"] = True
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -269,12 +272,13 @@ class Prober:
                 res = self._hip.run(ordinal, hbm_bytes=hbm, mfma=mfma,
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
                                     overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
-                                    host_link_bytes=hostlink)
+                                    host_link_bytes=hostlink, **({"lds_check": True} if lds else {}))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
                     (["--low-precision", ",".join(lowp)] if lowp else []) + \
-                    (["--host-link-bytes", str(hostlink)] if hostlink else [])
+                    (["--host-link-bytes", str(hostlink)] if hostlink else []) + \
+                    (["--lds-check"] if lds else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -322,7 +326,8 @@ class Prober:
     def explain(res: dict) -> dict:
         """A failed probe names what failed (HBM bits, GEMM element/ABFT mismatches, CU census;
         for spec.probe.mfmaLowPrecision the dtype in brackets; for spec.probe.hostLinkCheck the
-        bits flipped on the PCIe link and the host's sample of its own memory)."""
+        bits flipped on the PCIe link and the host's sample of its own memory; for
+        spec.probe.ldsCheck the bits flipped in a CU's LDS, or the CUs no workgroup reached)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -356,6 +361,18 @@ class Prober:
                 parts.append(f"{link['hostSampleMismatches']} of {link.get('hostSamples')} host "
                              f"samples differ")
             why.append("HostLinkMismatch: " + (", ".join(parts) or "check failed"))
+        lds = res.get("lds") or {}
+        if lds and not lds.get("ok", True):
+            if lds.get("badBits"):
+                k = int(lds.get("firstBadCU") or 0)  # the 11-bit key: xcc[10:8] se[7:5] sh[4] cu[3:0]
+                why.append(f"LDSPatternMismatch: {lds['badBits']} flipped bit(s) on {lds.get('badCUs')} "
+                           f"CU(s), first on CU {k >> 8}/{(k >> 5) & 7}/{(k >> 4) & 1}/{k & 15} at LDS "
+                           f"offset {lds.get('firstBadOffset')}")
+            # CUs no workgroup reached; without bad bits nothing else fails the block
+            expected = cus.get("expected")
+            if not lds.get("badBits") or (expected and lds.get("cusTested", 0) < expected):
+                why.append(f"LDSCoverageShort: {lds.get('cusVerified')}/{expected or '?'} CUs verified, "
+                           f"per XCD {lds.get('perXcd')}")
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

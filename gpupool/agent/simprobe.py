@@ -20,6 +20,10 @@ SIM_SWEEP_GBPS = 6000.0
 # the PCIe host link's slower direction (device -> host) at the default 4 MiB, alone on the GPU
 # (profiles/hostlink_rates.json)
 SIM_HOSTLINK_GBPS = 51.0
+# the LDS phase's grid factor and kernel time (native/src/probe/options.h lds::kBlocksPerCU,
+# profiles/lds_claim_probe_cost.json)
+SIM_LDS_BLOCKS_PER_CU = 4
+SIM_LDS_MS = 0.2
 SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
@@ -69,6 +73,24 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                            "writeGBps": SIM_HOSTLINK_GBPS, "readGBps": SIM_HOSTLINK_GBPS,
                            "GBps": SIM_HOSTLINK_GBPS, "ms": 4 * nbytes / (SIM_HOSTLINK_GBPS * 1e6),
                            "allocMs": 0.0}
+        if bad:
+            res["passed"] = False
+    # spec.probe.ldsCheck: the block the gfx950 probe reports; the overlay's ``ldsFault: n`` marks n
+    # CUs bad, one flipped bit each, the first on the CU with key 0 at LDS offset 0
+    if opts.get("ldsCheck"):
+        cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
+        bad = min(cus, int(fault(dev, "ldsFault") or 0))
+        per = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
+        left = bad
+        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
+            take = min(left, per[x])
+            per[x] -= take
+            left -= take
+        res["lds"] = {"ok": bad == 0, "bytesPerCU": 163840, "patterns": 2, "salt": 0,
+                      "workgroups": SIM_LDS_BLOCKS_PER_CU * cus, "cusTested": cus,
+                      "cusVerified": cus - bad, "perXcd": per, "badCUs": bad, "badBits": bad,
+                      "firstBadCU": 0 if bad else None, "firstBadOffset": 0 if bad else None,
+                      "ms": SIM_LDS_MS}
         if bad:
             res["passed"] = False
     if fail:

@@ -186,6 +186,11 @@ DEVICE_STATUS = {
                     "description": "The slower direction (GPU to host, host to GPU) of the "
                                    "spec.probe.hostLinkCheck PCIe test in GB/s (present only "
                                    "when the pool asks for the check)."},
+                "ldsVerifiedCUs": {
+                    **_I32,
+                    "description": "CUs whose whole LDS the spec.probe.ldsCheck march and address "
+                                   "test found clean (present only when the pool asks for the "
+                                   "check)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -416,6 +421,18 @@ MI355X_SPEC = {
                                                    "MI355X on PCIe Gen5 x16 measures ~51 at "
                                                    "the default 4 MiB, ~56 at 64 MiB, of the "
                                                    "63 GB/s spec rate."},
+                "ldsCheck": {**_B, "default": False,
+                             "description": "Also test the Local Data Share (160 KiB of SRAM) of "
+                                            "every CU at claim time and on rechecks: a workgroup "
+                                            "that owns the CU's whole LDS marches it in both "
+                                            "polarities with an address- and workgroup-dependent "
+                                            "pattern, each wave verifying what another wrote, then "
+                                            "address-tests it at dword granularity. A flipped bit "
+                                            "fails DeviceProbePassed (LDSPatternMismatch), and so "
+                                            "does a CU no workgroup reached (LDSCoverageShort); "
+                                            "the clean CUs are reported as "
+                                            "status.devices[].probe.ldsVerifiedCUs. Adds ~0.03 ms "
+                                            "to the 0.77 ms claim-time probe."},
                 "xgmiPeerCheck": {**_B, "default": True,
                                   "description": "For pools of 2+ GPUs: each GPU copies a "
                                                  "pattern to the next one over xGMI "

@@ -65,6 +65,9 @@ def lib() -> ctypes.CDLL:
                                                      ctypes.c_size_t]
                 l.mi355x_probe_host_link_geometry.restype = None
                 l.mi355x_probe_host_link_geometry.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
+            if hasattr(l, "mi355x_probe_lds"):  # absent from a library built before it
+                l.mi355x_probe_lds.restype = ctypes.c_void_p
+                l.mi355x_probe_lds.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
             if hasattr(l, "mi355x_probe_abft_check"):  # absent from a library built before them
                 vp, ull = ctypes.c_void_p, ctypes.c_ulonglong
                 l.mi355x_probe_abft_check.restype = ctypes.c_int
@@ -110,28 +113,32 @@ def identify(dev: int) -> dict:
 
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
-        host_link_bytes: int = 0, **test_hooks: int) -> dict:
+        host_link_bytes: int = 0, lds_check: bool = False, **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
     older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
     ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
     gemm_n GEMM with ABFT on that dtype's matrix-core instruction, reported under "lowp" (needs
     ``mfma``). ``host_link_bytes`` > 0 adds the PCIe host-link phase over that many bytes of pinned
     host memory (written and read back by the GPU over the link, every bit verified, both
-    directions timed), reported under "hostLink". ``test_hooks``: injectBitFlips=N (N bits spread over
+    directions timed), reported under "hostLink". ``lds_check`` adds the per-CU LDS phase (every
+    CU's 160 KiB marched in both polarities and address-tested by a workgroup that owns it),
+    reported under "lds"; its knobs and hooks (ldsBytes, ldsPatterns, ldsSalt, ldsBlocksPerCU,
+    ldsFirst, injectLdsFlipAtByte, injectLdsFaultXcc, injectLdsSkipChunk) go with the test hooks.
+    ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults;
     injectGemmFaultRow / injectGemmFaultCol place the GEMM fault (and injectLowpFault's) at that
     element of C instead of row gemm_n/3, column gemm_n/5 — outside C: no fault."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())),
-                     tuple(mfma_low_precision), int(host_link_bytes))
+                     tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check))
     return _take(lib().mi355x_probe_run(dev, opts))
 
 
 @functools.lru_cache(maxsize=64)
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
               gemm_tile: int, hooks: tuple, low_precision: tuple = (),
-              host_link_bytes: int = 0) -> bytes:
+              host_link_bytes: int = 0, lds_check: bool = False) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
     opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
@@ -140,6 +147,8 @@ def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps:
         opts["mfmaLowPrecision"] = lowp.dtype_mask(low_precision)
     if host_link_bytes > 0:  # absent when off: the default options stay what they were
         opts["hostLinkBytes"] = host_link_bytes
+    if lds_check:  # absent when off, likewise
+        opts["ldsCheck"] = 1
     return json.dumps(opts).encode()
 
 
@@ -179,6 +188,28 @@ def host_link(dev: int, nbytes: int, patterns: int = 2, preload=None, want_bytes
     res = _take(lib().mi355x_probe_host_link(dev, json.dumps(opts).encode(), buf, n))
     if buf is not None and want_bytes > 0 and "bytes" in res:
         res["data"] = buf.raw[:min(int(want_bytes), n, int(res["bytes"]))]
+    return res
+
+
+def lds(dev: int, nbytes: int = 163840, patterns: int = 2, want_stage: int = 0, **hooks: int) -> dict:
+    """The LDS phase alone (``mi355x_probe_lds``): every CU's Local Data Share marched over its
+    first ``nbytes`` (16 .. 163840, rounded down to 16) in ``patterns`` polarities and
+    address-tested. -> the "lds" block of ``run`` plus "device" and "passed". ``want_stage`` 1 | 2
+    | 3: workgroup 0's LDS as it stood after the first write / after the first complement write /
+    after the address pass's stores comes back under "data" (bytes; ``gpupool.ops.lds`` is its
+    numpy twin) and "dumpCU" names the CU it ran on. ``hooks``: ldsSalt, ldsBlocksPerCU,
+    requireAllCUs, injectLdsFlipAtByte, injectLdsFaultXcc, injectLdsSkipChunk."""
+    if not hasattr(lib(), "mi355x_probe_lds"):
+        raise RuntimeError("libmi355x_probe.so predates the LDS check: rebuild it")
+    opts = {"ldsBytes": int(nbytes), "ldsPatterns": int(patterns), **{k: int(v) for k, v in hooks.items()}}
+    buf, n = None, 0
+    if want_stage:
+        opts["ldsDumpStage"] = int(want_stage)
+        n = 163840
+        buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_lds(dev, json.dumps(opts).encode(), buf, n))
+    if buf is not None and "bytesPerCU" in res:
+        res["data"] = buf.raw[:int(res["bytesPerCU"])]
     return res
 
 

@@ -62,8 +62,33 @@ char* mi355x_probe_identify(int device);
  * "injectHostLinkFlipAtChunk":i — once the first write pass has completed (the one case with a
  * stream synchronise inside the phase) the HOST flips bit 0 of chunk i; out of range: no flip.
  * A/B knobs of the measurement sweep: "hostLinkGrid", "hostLinkUnroll" (4 | 8 | 16), "hostLinkNT",
- * "hostLinkCoherent", "hostLinkStream" (1: the tail of the MFMA stream). */
+ * "hostLinkCoherent", "hostLinkStream" (1: the tail of the MFMA stream).
+ *
+ * LDS (opt-in): "ldsCheck":1 tests the Local Data Share of every CU. One kernel of 256-thread workgroups,
+ * each declaring the CU's whole 163,840-byte LDS (so it has the CU's LDS to itself), "ldsBlocksPerCU" of
+ * them per CU: per polarity ("ldsPatterns", default 2, 1..4) a march — write the workgroup- and
+ * address-dependent pattern, verify it from another wave and write the complement, verify that from a
+ * third — then an address pass at dword granularity through 4-byte stores in a strided order, read back
+ * 16 bytes at a time. "ldsBytes" (default and maximum 163840, at least 16, rounded down to 16) is what of
+ * the LDS is tested; seed (0x4C445300 + device) ^ "ldsSalt" (default: a per-device run counter). It runs on
+ * the MFMA stream ahead of the MFMA phase ("ldsFirst":0 behind it and the low-precision phases), with
+ * "overlap":0 last on the one stream. The report then gains, after "hostLink",
+ *   "lds":{"ok","bytesPerCU","patterns","salt","workgroups","cusTested","cusVerified","perXcd","badCUs",
+ *          "badBits","firstBadCU","firstBadOffset","ms"}
+ * cusVerified = tested and not bad, perXcd the verified CUs per XCD, firstBadCU the 11-bit CU key
+ * (xcc[10:8] se[7:5] sh[4] cu[3:0]) and firstBadOffset the byte offset of the lowest fault or null;
+ * ok = no bad bit and, unless "requireAllCUs":0, every CU verified; "passed" also needs it. Without the
+ * option: no "lds" key, no launch, allocation or event. Test hooks, all plain LDS stores:
+ * "injectLdsFlipAtByte":o (bit 0 of byte o in every workgroup after the first write; out of range: none),
+ * "injectLdsFaultXcc":x (that flip only on XCD x), "injectLdsSkipChunk":j (the first write leaves chunk j). */
 char* mi355x_probe_run(int device, const char* opts_json);
+/* The LDS phase alone, on the device's first stream, under the device's probe lock; the "lds" block (after
+ * "device" and "passed") is the whole report. opts as above (without "ldsCheck"). With image and
+ * "ldsDumpStage":1|2|3, workgroup 0's LDS is copied out — 1 after the first write, 2 after the first
+ * complement write, 3 after the address pass's stores — its first min(image_bytes, tested bytes) land in
+ * image and the report names "dumpCU", the CU key that workgroup ran on. A bad device or an "ldsBytes"
+ * outside [16, 163840]: {"passed":false,"error":...}. */
+char* mi355x_probe_lds(int device, const char* opts_json, void* image, size_t image_bytes);
 /* The host-link phase alone, on the device's first stream, under the device's probe lock; the
  * "hostLink" block (after "device" and "passed") is the whole report. opts as above ("hostLinkBytes",
  * "hostLinkPatterns", the hook, the knobs). io may be NULL; after the run the first min(io_bytes, bytes)

@@ -45,6 +45,15 @@ struct DeviceCtx {
   bool hl_coherent = true;
   unsigned long long* hl_cnt = nullptr;  // device counter pairs, one per pass
   unsigned long long* hl_res = nullptr;  // their pinned copy
+  // LDS phase ("ldsCheck"): created by the first probe that asks. Two sets of device counters: the
+  // kernel of one run counts into set lds_set and resets the other for the next run (lds.h).
+  hipEvent_t lds_ev[2] = {};
+  unsigned long long* lds_cnt = nullptr;  // device, 2 sets
+  unsigned long long* lds_res = nullptr;  // pinned copy of the set a run used
+  int lds_set = 0;
+  bool lds_clean = false;    // both sets hold their reset values
+  uint32_t lds_runs = 0;     // the default "ldsSalt"
+  void* lds_dump = nullptr;  // device copy of workgroup 0's LDS (mi355x_probe_lds with an image)
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;

@@ -143,6 +143,79 @@ struct Plan {
 
 }  // namespace hostlink
 
+namespace lds {
+
+// The LDS of one gfx950 CU, which one workgroup of the phase's kernel declares in full.
+constexpr uint32_t kBytesPerCU = 163840;
+// Workgroups per CU of the grid ("ldsBlocksPerCU" selects per run): the oversubscription that makes
+// the dispatcher visit every CU, like the census's 8. Measured on the MI355X, 200 runs per factor
+// (scripts/lds_claim_probe_cost.py, profiles/lds_claim_probe_cost.json): alone on the GPU every
+// factor from 1 up tested all 256 CUs in every run; inside the overlapped claim probe 1 and 2 each
+// had a run that reached 212 / 218 CUs, 4, 8 and 16 none. The kernel's time is linear in the factor
+// (alone 0.048 ms per workgroup per CU), so the default is the smallest factor that never fell short.
+constexpr int kBlocksPerCU = 4;
+constexpr int kMaxBlocksPerCU = 64;
+// Where the phase sits on the MFMA stream ("ldsFirst" selects per run): 0 behind the MFMA and
+// low-precision phases, 1 ahead of them. Same measurement, 40 alternating rounds: ahead of the MFMA
+// phase the kernel overlaps the HBM test's first fill, which needs no LDS, and the claim probe grows
+// by a quarter of what the tail position adds.
+constexpr int kFirst = 1;
+
+// The address pass writes dword ((t + 256 i) * S) mod N: S is the smallest odd value >= 33 that is
+// coprime to N, so d -> d * S mod N is a bijection of the N tested dwords and neighbouring threads
+// land 33+ dwords apart. A wrong S leaves dwords unwritten, which the pass then reports.
+inline uint32_t stride_for(uint32_t dwords) {
+  auto gcd = [](uint32_t a, uint32_t b) {
+    while (b) {
+      const uint32_t r = a % b;
+      a = b;
+      b = r;
+    }
+    return a;
+  };
+  uint32_t s = 33;
+  while (gcd(s, dwords) != 1) s += 2;
+  return s;
+}
+
+// What one run of the phase does (options of mi355x_probe_run with "ldsCheck" and of mi355x_probe_lds).
+struct Plan {
+  uint32_t n16 = 0;  // tested 16-byte chunks per workgroup; 0: the phase is off
+  int patterns = 2;
+  bool salt_given = false;  // else the phase takes the context's run counter
+  uint32_t salt = 0;        // "ldsSalt", XORed into the seed
+  uint32_t seed = 0;        // 0x4C445300 + dev, before the salt
+  int blocks_per_cu = kBlocksPerCU;
+  long long flip_byte = -1;   // test hook "injectLdsFlipAtByte"
+  int fault_xcc = -1;         // test hook "injectLdsFaultXcc": the flip only on that XCD
+  long long skip_chunk = -1;  // test hook "injectLdsSkipChunk"
+  int dump_stage = 0;         // "ldsDumpStage" 1 | 2 | 3, only with a caller buffer
+  uint32_t stride() const { return stride_for(n16 * 4); }
+  // "ldsBytes": 16 .. kBytesPerCU, rounded down to whole chunks; anything else throws.
+  static Plan parse(const char* json, int dev) {
+    Plan pl;
+    const long long bytes = opt_int(json, "ldsBytes", kBytesPerCU);
+    if (bytes < 16 || bytes > static_cast<long long>(kBytesPerCU))
+      throw std::invalid_argument("ldsBytes outside [16, 163840]");
+    pl.n16 = static_cast<uint32_t>(bytes / 16);
+    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "ldsPatterns", 2))));
+    const long long salt = opt_int(json, "ldsSalt", -1);
+    pl.salt_given = salt >= 0;
+    pl.salt = pl.salt_given ? static_cast<uint32_t>(salt) : 0u;
+    pl.seed = 0x4C445300u + static_cast<uint32_t>(dev);
+    pl.blocks_per_cu =
+        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "ldsBlocksPerCU", kBlocksPerCU))));
+    pl.flip_byte = opt_int(json, "injectLdsFlipAtByte", -1);
+    pl.fault_xcc = static_cast<int>(opt_int(json, "injectLdsFaultXcc", -1));
+    pl.skip_chunk = opt_int(json, "injectLdsSkipChunk", -1);
+    const long long stage = opt_int(json, "ldsDumpStage", 0);
+    pl.dump_stage = stage >= 1 && stage <= 3 ? static_cast<int>(stage) : 0;
+    return pl;
+  }
+};
+
+}  // namespace lds
+
 // Where the GEMM fault hooks corrupt C (test hooks "injectGemmFaultRow" / "injectGemmFaultCol"):
 // -1 is the element the hooks always took, row n/3 and column n/5; any other value outside [0, n)
 // means no fault, like "injectFlipAtChunk".
@@ -196,6 +269,8 @@ struct ProbeOptions {
   bool keep_arena = true;
   hostlink::Plan host_link;        // n16 == 0: off, and none of its options is looked up
   bool host_link_on_mfma_stream = false;  // "hostLinkStream":1, for the A/B; only with overlap
+  lds::Plan lds;                   // "ldsCheck"; n16 == 0: off, and none of its options is looked up
+  bool lds_first = lds::kFirst == 1;  // "ldsFirst": 1 ahead of the MFMA phase on its stream, 0 behind it (A/B)
 
   static ProbeOptions parse(const char* json, int dev = 0) {
     ProbeOptions o;
@@ -232,6 +307,11 @@ struct ProbeOptions {
     if (hl_bytes) {
       o.host_link = hostlink::Plan::parse(json, dev, hl_bytes);
       o.host_link_on_mfma_stream = o.overlap && opt_int(json, "hostLinkStream", 0) == 1;
+    }
+    if (opt_bool(json, "ldsCheck", false)) {
+      o.lds = lds::Plan::parse(json, dev);
+      o.lds.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_lds
+      o.lds_first = opt_int(json, "ldsFirst", lds::kFirst) == 1;
     }
     return o;
   }

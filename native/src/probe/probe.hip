@@ -31,6 +31,7 @@
 //   mfma_phase.h     the GEMM dispatch and the bf16 MFMA phase (launch / finish)
 //   lowp.h           FP8 / MXFP8 / MXFP4 phase ("mfmaLowPrecision")
 //   hostlink.h       PCIe host-link phase ("hostLinkBytes")
+//   lds.h            per-CU LDS march and address test ("ldsCheck")
 //   ctx.h            per-device state and ensure_ctx(); peer.h the xGMI checks; sweep.h the HBM sweep
 #include <hip/hip_runtime.h>
 
@@ -48,6 +49,7 @@
 #include "ctx.h"
 #include "hbm.h"
 #include "hostlink.h"
+#include "lds.h"
 #include "lowp.h"
 #include "mfma_phase.h"
 #include "options.h"
@@ -182,6 +184,8 @@ std::string run_probe(int dev, const char* opts) {
     hl.alloc_ms = hostlink::ensure(ctx, hl.n16 * 16, hl.coherent);
     hl_s = host_link_stream(ctx, o);
   }
+  lds::Plan ld = o.lds;
+  if (ld.n16) lds::ensure(ctx, false);
   ProbeReport rep;
   PhaseTimes& t = rep.phases;
   t.hbm_first = o.hbm_first;
@@ -197,19 +201,30 @@ std::string run_probe(int dev, const char* opts) {
   t.alloc_ms = ms_since(t_alloc);
 
   // enqueue: the HBM test on s, the MFMA phase and the low-precision phase behind it on s2, in
-  // "hbmFirst" order; the host link after both, so it overlaps both
+  // "hbmFirst" order; the host link after both, so it overlaps both. The LDS phase ("ldsCheck")
+  // never gets a stream of its own: ahead of the MFMA phase on s2, where it overlaps the first HBM
+  // fill ("ldsFirst":0 behind it and the low-precision phase), or serial, last on the one stream
   auto t_run = std::chrono::steady_clock::now();
   reset_counters(ctx, o, cnt, s, s2);
   const lowp::Phase lp = lowp_phase(ctx, o, base, lay);
+  bool lds_pending = ld.n16 != 0;
+  auto enqueue_lds = [&](bool here) {
+    if (!lds_pending || !here) return;
+    lds::launch(ctx, s2, ld);
+    lds_pending = false;
+  };
   auto enqueue_mfma = [&](int when) {
     if (!o.mfma || o.hbm_first != when) return;
+    enqueue_lds(o.overlap && o.lds_first);
     launch_mfma_phase(base, lay, o, ctx, s2);
     lowp::launch(s2, lp);
+    enqueue_lds(o.overlap);
   };
   const PatternPass pass = hbm_pass(ctx, o, dev, base, lay, n16);
   enqueue_mfma(0);
   enqueue_hbm(ctx, pass, o, cnt, [&] { enqueue_mfma(2); });
   enqueue_mfma(1);
+  enqueue_lds(true);  // serial, or no MFMA phase to follow
   if (hl.n16) hostlink::launch(ctx, hl_s, hl);
   t.launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
 
@@ -223,6 +238,11 @@ std::string run_probe(int dev, const char* opts) {
   if (o.mfma) {
     PROBE_CHECK(hipStreamSynchronize(s2));
     finish_mfma(o, ctx, &rep.mfma, &rep.cus);
+  }
+  rep.has_lds = ld.n16 != 0;
+  if (ld.n16) {
+    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
+    rep.lds = lds::finish(ctx, ld, o.require_all_cus);
   }
   rep.lowp = lowp::finish(lp, o.require_all_cus);
   t.mfma_wall_ms = o.mfma ? ms_since(t_run) : 0.0;
@@ -709,6 +729,26 @@ char* mi355x_probe_host_link(int dev, const char* opts_json, void* io, size_t io
 
 int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int m, int n, int k) {
   return mi355x_probe_gemm_bf16_opts(dev, A, Bt, C, m, n, k, nullptr);
+}
+
+char* mi355x_probe_lds(int dev, const char* opts_json, void* image, size_t image_bytes) {
+  if (!device_ok(dev)) return bad_device();
+  ProbeActive active;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded(device_head(dev), [&] {
+    lds::Plan pl = lds::Plan::parse(opts_json, dev);  // throws on a size outside [16, 163840]
+    if (!image || !image_bytes) pl.dump_stage = 0;
+    DeviceCtx& ctx = ensure_ctx(dev);
+    lds::ensure(ctx, pl.dump_stage != 0);
+    lds::launch(ctx, ctx.stream, pl);
+    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
+    const LdsResult r = lds::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
+    if (pl.dump_stage)
+      PROBE_CHECK(hipMemcpy(image, ctx.lds_dump, std::min<size_t>(image_bytes, static_cast<size_t>(pl.n16) * 16),
+                            hipMemcpyDeviceToHost));
+    // the block is the whole report, with the usual head
+    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + lds_block(r).substr(1);
+  });
 }
 
 void mi355x_probe_free(char* p) { std::free(p); }

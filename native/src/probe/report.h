@@ -143,6 +143,38 @@ inline std::string host_link_block(const HostLinkResult& r) {
          ",\"ms\":" + jnum((r.preload ? 0.0 : p.write_ms) + p.read_ms) + ",\"allocMs\":" + jnum(r.alloc_ms) + "}";
 }
 
+// The LDS phase: which CUs a workgroup marched the LDS of, and what it found there. first_bad is
+// (CU key << 32) | byte offset of the lowest faulting byte, all-ones = none.
+struct LdsResult {
+  uint64_t bytes_per_cu = 0;
+  int patterns = 0;
+  uint32_t salt = 0;
+  unsigned long long workgroups = 0;
+  int expected = 0, tested = 0, verified = 0, bad_cus = 0;
+  int per_xcd[8] = {};  // verified
+  unsigned long long bad_bits = 0, first_bad = ~0ull;
+  float ms = 0;
+  bool require_all = true;  // "requireAllCUs"
+  int dump_cu = -1;         // mi355x_probe_lds with an image: the CU key of the dumped workgroup
+  bool ok() const { return bad_bits == 0 && (!require_all || verified >= expected); }
+};
+
+inline std::string lds_block(const LdsResult& r) {
+  std::string per = "[";
+  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
+  const bool none = r.first_bad == ~0ull;
+  std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"bytesPerCU\":" + std::to_string(r.bytes_per_cu) +
+                    ",\"patterns\":" + std::to_string(r.patterns) + ",\"salt\":" + std::to_string(r.salt) +
+                    ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"cusTested\":" + std::to_string(r.tested) +
+                    ",\"cusVerified\":" + std::to_string(r.verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badBits\":" + std::to_string(r.bad_bits) +
+                    ",\"firstBadCU\":" + (none ? std::string("null") : std::to_string(r.first_bad >> 32)) +
+                    ",\"firstBadOffset\":" + (none ? std::string("null") : std::to_string(r.first_bad & 0xFFFFFFFFull)) +
+                    ",\"ms\":" + jnum(r.ms);
+  if (r.dump_cu >= 0) out += ",\"dumpCU\":" + std::to_string(r.dump_cu);
+  return out + "}";
+}
+
 // Host wall-clock of a probe's steps.
 struct PhaseTimes {
   bool arena_reused = false;
@@ -162,7 +194,7 @@ inline std::string phases_block(const PhaseTimes& t) {
 inline std::string device_head(int dev) { return "\"device\":" + std::to_string(dev); }
 
 // Everything mi355x_probe_run reports. "cus" only with the MFMA phase, "lowp" only with a dtype,
-// "hostLink" only when asked for.
+// "hostLink" and "lds" only when asked for.
 struct ProbeReport {
   int dev = 0;
   std::string uuid, arch;
@@ -172,10 +204,12 @@ struct ProbeReport {
   std::vector<LowpResult> lowp;
   bool has_host_link = false;
   HostLinkResult host_link;
+  bool has_lds = false;
+  LdsResult lds;
   double total_ms = 0;
   PhaseTimes phases;
   bool passed() const {
-    bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok());
+    bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok()) && (!has_lds || lds.ok());
     for (const LowpResult& l : lowp) ok = ok && l.ok;
     return ok;
   }
@@ -195,6 +229,7 @@ inline std::string probe_report_open(const ProbeReport& r) {
   if (r.mfma.enabled) out += ",\"cus\":" + cus_block(r.cus);
   if (!r.lowp.empty()) out += ",\"lowp\":" + lowp_block(r.lowp);
   if (r.has_host_link) out += ",\"hostLink\":" + host_link_block(r.host_link);
+  if (r.has_lds) out += ",\"lds\":" + lds_block(r.lds);
   out += ",\"ms\":" + jnum(r.total_ms);
   out += ",\"phases\":" + phases_block(r.phases);
   return out;

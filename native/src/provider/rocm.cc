@@ -95,6 +95,8 @@ Json DeviceView::status_json() const {
     }
     if (probe["hostLink"].is_object())  // spec.probe.hostLinkCheck: the slower direction of the PCIe test
       p["hostLinkGBps"] = probe.path("hostLink.GBps");
+    if (probe["lds"].is_object())  // spec.probe.ldsCheck: the CUs whose whole LDS tested clean
+      p["ldsVerifiedCUs"] = probe.path("lds.cusVerified");
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)
