@@ -240,6 +240,7 @@ class Prober:
         hostlink = int(opts.get("hostLinkBytes") or schema.DEFAULT_HOST_LINK_BYTES) \
             if opts.get("hostLinkCheck") else 0
         lds = bool(opts.get("ldsCheck"))  # spec.probe.ldsCheck: the per-CU LDS phase
+        regs = bool(opts.get("registerCheck"))  # spec.probe.registerCheck: the register-file phase
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -259,6 +260,8 @@ class Prober:
                 args["hostLinkBytes"] = hostlink
             if lds:
                 args["ldsCheck"] = True
+            if regs:
+                args["registerCheck"] = True
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -272,13 +275,14 @@ class Prober:
                 res = self._hip.run(ordinal, hbm_bytes=hbm, mfma=mfma,
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
                                     overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
-                                    host_link_bytes=hostlink, **({"lds_check": True} if lds else {}))
+                                    host_link_bytes=hostlink, **({"lds_check": True} if lds else {}),
+                                    **({"reg_check": True} if regs else {}))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
                     (["--low-precision", ",".join(lowp)] if lowp else []) + \
                     (["--host-link-bytes", str(hostlink)] if hostlink else []) + \
-                    (["--lds-check"] if lds else [])
+                    (["--lds-check"] if lds else []) + (["--register-check"] if regs else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -327,7 +331,9 @@ class Prober:
         """A failed probe names what failed (HBM bits, GEMM element/ABFT mismatches, CU census;
         for spec.probe.mfmaLowPrecision the dtype in brackets; for spec.probe.hostLinkCheck the
         bits flipped on the PCIe link and the host's sample of its own memory; for
-        spec.probe.ldsCheck the bits flipped in a CU's LDS, or the CUs no workgroup reached)."""
+        spec.probe.ldsCheck the bits flipped in a CU's LDS, or the CUs no workgroup reached; for
+        spec.probe.registerCheck the bits flipped in a SIMD's vector register file, the CUs not
+        covered, or a kernel that did not own the file it tested)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -373,6 +379,25 @@ class Prober:
             if not lds.get("badBits") or (expected and lds.get("cusTested", 0) < expected):
                 why.append(f"LDSCoverageShort: {lds.get('cusVerified')}/{expected or '?'} CUs verified, "
                            f"per XCD {lds.get('perXcd')}")
+        regs = res.get("regs") or {}
+        if regs and not regs.get("ok", True):
+            if regs.get("badBits"):
+                k = int(regs.get("firstBadCU") or 0)  # the 11-bit key: xcc[10:8] se[7:5] sh[4] cu[3:0]
+                u = int(regs.get("firstBadRegister") or 0)  # unified: v0..v255 then a0..a255
+                why.append(f"RegisterFileMismatch: {regs['badBits']} flipped bit(s) on {regs.get('badCUs')} "
+                           f"CU(s), first on CU {k >> 8}/{(k >> 5) & 7}/{(k >> 4) & 1}/{k & 15} SIMD "
+                           f"{regs.get('firstBadSimd')} register {'v%d' % u if u < 256 else 'a%d' % (u - 256)} "
+                           f"lane {regs.get('firstBadLane')}")
+            exclusive = regs.get("registersPerLane") == 512 and regs.get("workgroupsPerCU") == 1
+            if not exclusive:
+                why.append(f"RegisterKernelNotExclusive: {regs.get('registersPerLane')} registers per lane, "
+                           f"{regs.get('workgroupsPerCU')} workgroup(s) per CU")
+            # CUs no workgroup covered with four SIMDs; without the above nothing else fails the block
+            expected = cus.get("expected")
+            if (exclusive and not regs.get("badBits")) or regs.get("simdShort") or \
+                    (expected and regs.get("cusTested", 0) < expected):
+                why.append(f"RegisterCoverageShort: {regs.get('cusVerified')}/{expected or '?'} CUs verified, "
+                           f"per XCD {regs.get('perXcd')}, {regs.get('simdShort')} workgroup(s) on fewer than 4 SIMDs")
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

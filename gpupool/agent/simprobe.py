@@ -24,6 +24,10 @@ SIM_HOSTLINK_GBPS = 51.0
 # profiles/lds_claim_probe_cost.json)
 SIM_LDS_BLOCKS_PER_CU = 4
 SIM_LDS_MS = 0.2
+# the register-file phase's grid factor and kernel time (native/src/probe/options.h
+# regs::kBlocksPerCU, profiles/regs_claim_probe_cost.json)
+SIM_REGS_BLOCKS_PER_CU = 2
+SIM_REGS_MS = 0.15
 SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
@@ -91,6 +95,25 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                       "cusVerified": cus - bad, "perXcd": per, "badCUs": bad, "badBits": bad,
                       "firstBadCU": 0 if bad else None, "firstBadOffset": 0 if bad else None,
                       "ms": SIM_LDS_MS}
+        if bad:
+            res["passed"] = False
+    # spec.probe.registerCheck: the block the gfx950 probe reports; the overlay's ``regFault: n``
+    # marks n CUs bad, one flipped bit each, the first on the CU with key 0, SIMD 0, register v17, lane 0
+    if opts.get("registerCheck"):
+        cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
+        bad = min(cus, int(fault(dev, "regFault") or 0))
+        per = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
+        left = bad
+        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
+            take = min(left, per[x])
+            per[x] -= take
+            left -= take
+        res["regs"] = {"ok": bad == 0, "registersPerLane": 512, "workgroupsPerCU": 1, "patterns": 2,
+                       "salt": 0, "workgroups": SIM_REGS_BLOCKS_PER_CU * cus, "cusTested": cus,
+                       "cusVerified": cus - bad, "simdsTested": 4 * cus, "simdShort": 0, "perXcd": per,
+                       "badCUs": bad, "badBits": bad, "firstBadCU": 0 if bad else None,
+                       "firstBadSimd": 0 if bad else None, "firstBadRegister": 17 if bad else None,
+                       "firstBadLane": 0 if bad else None, "ms": SIM_REGS_MS}
         if bad:
             res["passed"] = False
     if fail:

@@ -191,6 +191,11 @@ DEVICE_STATUS = {
                     "description": "CUs whose whole LDS the spec.probe.ldsCheck march and address "
                                    "test found clean (present only when the pool asks for the "
                                    "check)."},
+                "regsVerifiedCUs": {
+                    **_I32,
+                    "description": "CUs on whose four SIMDs the spec.probe.registerCheck march found "
+                                   "the whole vector register file clean (present only when the "
+                                   "pool asks for the check)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -433,6 +438,22 @@ MI355X_SPEC = {
                                             "the clean CUs are reported as "
                                             "status.devices[].probe.ldsVerifiedCUs. Adds ~0.03 ms "
                                             "to the 0.77 ms claim-time probe."},
+                "registerCheck": {**_B, "default": False,
+                                  "description": "Also test the vector register file (VGPRs and "
+                                                 "AGPRs: 512 registers x 64 lanes per SIMD, 512 KiB "
+                                                 "per CU) of every SIMD of every CU at claim time and "
+                                                 "on rechecks: a workgroup whose kernel asks for all "
+                                                 "512 registers, and so owns the CU, marches every "
+                                                 "register in both polarities with a register-, "
+                                                 "lane- and workgroup-dependent pattern. A flipped "
+                                                 "bit fails DeviceProbePassed (RegisterFileMismatch), "
+                                                 "and so does a CU not covered on all four SIMDs "
+                                                 "(RegisterCoverageShort) or a kernel that did not "
+                                                 "own its CU (RegisterKernelNotExclusive); the clean "
+                                                 "CUs are reported as "
+                                                 "status.devices[].probe.regsVerifiedCUs. "
+                                                 "Adds ~0.06 ms to the 0.77 ms claim-time "
+                                                 "probe."},
                 "xgmiPeerCheck": {**_B, "default": True,
                                   "description": "For pools of 2+ GPUs: each GPU copies a "
                                                  "pattern to the next one over xGMI "

@@ -68,6 +68,9 @@ def lib() -> ctypes.CDLL:
             if hasattr(l, "mi355x_probe_lds"):  # absent from a library built before it
                 l.mi355x_probe_lds.restype = ctypes.c_void_p
                 l.mi355x_probe_lds.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
+            if hasattr(l, "mi355x_probe_regs"):  # absent from a library built before it
+                l.mi355x_probe_regs.restype = ctypes.c_void_p
+                l.mi355x_probe_regs.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
             if hasattr(l, "mi355x_probe_abft_check"):  # absent from a library built before them
                 vp, ull = ctypes.c_void_p, ctypes.c_ulonglong
                 l.mi355x_probe_abft_check.restype = ctypes.c_int
@@ -113,7 +116,8 @@ def identify(dev: int) -> dict:
 
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
-        host_link_bytes: int = 0, lds_check: bool = False, **test_hooks: int) -> dict:
+        host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False,
+        **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
     older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
     ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
@@ -124,21 +128,30 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     CU's 160 KiB marched in both polarities and address-tested by a workgroup that owns it),
     reported under "lds"; its knobs and hooks (ldsBytes, ldsPatterns, ldsSalt, ldsBlocksPerCU,
     ldsFirst, injectLdsFlipAtByte, injectLdsFaultXcc, injectLdsSkipChunk) go with the test hooks.
+    ``reg_check`` adds the register-file phase (all 512 vector registers of every lane of every SIMD
+    of every CU marched in both polarities by a workgroup that owns the CU), reported under "regs";
+    its knobs and hooks (regsPatterns, regsSalt, regsBlocksPerCU, regsFirst, injectRegFlip=[u, lane,
+    bit], injectRegFaultSimd, injectRegFaultXcc, injectRegSkip) go with the test hooks too.
     ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults;
     injectGemmFaultRow / injectGemmFaultCol place the GEMM fault (and injectLowpFault's) at that
     element of C instead of row gemm_n/3, column gemm_n/5 — outside C: no fault."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
-                     int(gemm_tile), tuple(sorted((k, int(v)) for k, v in test_hooks.items())),
-                     tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check))
+                     int(gemm_tile), tuple(sorted((k, _hook(v)) for k, v in test_hooks.items())),
+                     tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check), bool(reg_check))
     return _take(lib().mi355x_probe_run(dev, opts))
+
+
+def _hook(v):
+    """A hook's value: an integer, or a tuple of them (injectRegFlip)."""
+    return tuple(int(x) for x in v) if isinstance(v, (list, tuple)) else int(v)
 
 
 @functools.lru_cache(maxsize=64)
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
               gemm_tile: int, hooks: tuple, low_precision: tuple = (),
-              host_link_bytes: int = 0, lds_check: bool = False) -> bytes:
+              host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
     opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
@@ -149,6 +162,8 @@ def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps:
         opts["hostLinkBytes"] = host_link_bytes
     if lds_check:  # absent when off, likewise
         opts["ldsCheck"] = 1
+    if reg_check:
+        opts["regCheck"] = 1
     return json.dumps(opts).encode()
 
 
@@ -210,6 +225,33 @@ def lds(dev: int, nbytes: int = 163840, patterns: int = 2, want_stage: int = 0, 
     res = _take(lib().mi355x_probe_lds(dev, json.dumps(opts).encode(), buf, n))
     if buf is not None and "bytesPerCU" in res:
         res["data"] = buf.raw[:int(res["bytesPerCU"])]
+    return res
+
+
+def regs(dev: int, patterns: int = 2, want_stage: int = 0, **hooks) -> dict:
+    """The register-file phase alone (``mi355x_probe_regs``): the 512 vector registers (v0..v255,
+    a0..a255) of every lane of every SIMD of every CU marched in ``patterns`` polarities. -> the
+    "regs" block of ``run`` plus "device" and "passed". ``want_stage`` 1 | 2: workgroup 0's
+    registers as they stood after the first write / after the first complement write come back
+    under "data" (uint32 [4][512][64]: wave, register, lane; ``gpupool.ops.regfile`` is the numpy
+    twin), "dumpCU" names the CU it ran on and "dumpSimds" the SIMD of each of its waves.
+    ``hooks``: regsSalt, regsBlocksPerCU, requireAllCUs, injectRegFlip=[u, lane, bit],
+    injectRegFaultSimd, injectRegFaultXcc, injectRegSkip."""
+    import numpy as np
+
+    from . import regfile
+    if not hasattr(lib(), "mi355x_probe_regs"):
+        raise RuntimeError("libmi355x_probe.so predates the register-file check: rebuild it")
+    opts = {"regsPatterns": int(patterns), **{k: _hook(v) for k, v in hooks.items()}}
+    buf, n = None, 0
+    if want_stage:
+        opts["regsDumpStage"] = int(want_stage)
+        n = regfile.IMAGE_BYTES
+        buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_regs(dev, json.dumps(opts).encode(), buf, n))
+    if buf is not None and "dumpCU" in res:
+        res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(regfile.WAVES, regfile.REGISTERS,
+                                                                   regfile.LANES).copy()
     return res
 
 

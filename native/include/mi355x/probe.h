@@ -80,8 +80,43 @@ char* mi355x_probe_identify(int device);
  * ok = no bad bit and, unless "requireAllCUs":0, every CU verified; "passed" also needs it. Without the
  * option: no "lds" key, no launch, allocation or event. Test hooks, all plain LDS stores:
  * "injectLdsFlipAtByte":o (bit 0 of byte o in every workgroup after the first write; out of range: none),
- * "injectLdsFaultXcc":x (that flip only on XCD x), "injectLdsSkipChunk":j (the first write leaves chunk j). */
+ * "injectLdsFaultXcc":x (that flip only on XCD x), "injectLdsSkipChunk":j (the first write leaves chunk j).
+ *
+ * Register files (opt-in): "regCheck":1 tests the vector register file of every SIMD of every CU: the 512
+ * registers per lane (v0..v255 numbered u = 0..255, a0..a255 numbered 256..511) of all 64 lanes. One kernel
+ * of 256-thread workgroups whose descriptor asks for all 512 registers, so a SIMD holds one wave of it and a
+ * workgroup has its CU to itself, "regsBlocksPerCU" of them per CU (default 2, 1..64). Register u of lane l of
+ * wave w of workgroup b is expected to hold (base + u * 0x9E3779B1) ^ flip, base the first word of pattern16
+ * of index (b << 32) | (64 w + l), seed (0x52454700 + device) ^ "regsSalt" (default: a per-device run
+ * counter). Per polarity ("regsPatterns", default 2, 1..4): write every register ascending, verify each
+ * ascending and write its complement (computed from the expected value), verify the complements descending.
+ * AGPRs are moved only by v_accvgpr_write_b32 / v_accvgpr_read_b32; the march is two asm statements, one over
+ * v16..v255 and a0..a255 with the compiler's operands below v16, one over v0..v15. It runs on the MFMA stream
+ * behind the MFMA and low-precision phases ("regsFirst":1 ahead of them), behind the LDS phase where both
+ * are asked for, with "overlap":0 last on the one stream. The report then gains, after "lds",
+ *   "regs":{"ok","registersPerLane","workgroupsPerCU","patterns","salt","workgroups","cusTested","cusVerified",
+ *           "simdsTested","simdShort","perXcd","badCUs","badBits","firstBadCU","firstBadSimd",
+ *           "firstBadRegister","firstBadLane","ms"}
+ * registersPerLane / workgroupsPerCU are what the runtime says of the kernel (hipFuncGetAttributes,
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor): anything but 512 and 1 fails the phase and adds
+ * "error":"RegisterKernelNotExclusive" to the block. A workgroup marks its CU tested only when its four
+ * waves read four different SIMD ids (HW_ID[5:4]), else it counts into simdShort; simdsTested = 4 x
+ * cusTested; cusVerified = tested and not bad, perXcd the verified CUs per XCD; firstBadCU (the 11-bit CU
+ * key), firstBadSimd, firstBadRegister (the unified index u) and firstBadLane name the lowest fault, or are
+ * null. ok = no bad bit, the kernel exclusive, simdShort 0 and, unless "requireAllCUs":0, every CU verified;
+ * "passed" also needs it. Without the option: no "regs" key, no launch, allocation or event. Test hooks (any
+ * of them, or the dump below, selects the kernel's test instantiation; the production one carries none):
+ * "injectRegFlip":[u, lane, bit] (that bit of register u in that lane of every wave, after the first write),
+ * "injectRegFaultSimd":s / "injectRegFaultXcc":x (that flip only on SIMD s / on XCD x), "injectRegSkip":u
+ * (the first write leaves register u alone); a value out of range switches its hook off. */
 char* mi355x_probe_run(int device, const char* opts_json);
+/* The register-file phase alone, on the device's first stream, under the device's probe lock; the "regs"
+ * block (after "device" and "passed") is the whole report. opts as above (without "regCheck"). With image
+ * and "regsDumpStage":1|2, workgroup 0's registers are stored to a device image uint32[4][512][64] (wave,
+ * register u, lane) — 1 after the first write, 2 after the first complement write — whose first
+ * min(image_bytes, 524288) bytes land in image, and the report names "dumpCU", the CU key that workgroup ran
+ * on, and "dumpSimds", the SIMD of each of its four waves. A bad device: {"passed":false,"error":...}. */
+char* mi355x_probe_regs(int device, const char* opts_json, void* image, size_t image_bytes);
 /* The LDS phase alone, on the device's first stream, under the device's probe lock; the "lds" block (after
  * "device" and "passed") is the whole report. opts as above (without "ldsCheck"). With image and
  * "ldsDumpStage":1|2|3, workgroup 0's LDS is copied out — 1 after the first write, 2 after the first

@@ -85,6 +85,7 @@ Mi355xPoolSpec Mi355xPoolSpec::from(const Json& s) {
   p.probe_host_link_bytes = pr["hostLinkBytes"].as_int(gen::kDefaultProbeHostLinkBytes);
   p.probe_min_host_link_gbps = pr["minHostLinkGBps"].as_double(0);
   p.probe_lds_check = pr["ldsCheck"].as_bool(false);
+  p.probe_register_check = pr["registerCheck"].as_bool(false);
   p.probe_min_hbm_gbps = pr["minHbmGBps"].as_double(0);
   p.probe_min_mfma_tflops = pr["minMfmaTflops"].as_double(0);
   p.probe_recheck_seconds = pr["recheckSeconds"].as_int(0);
@@ -121,6 +122,7 @@ Json Mi355xPoolSpec::probe_json() const {
     j["minHostLinkGBps"] = probe_min_host_link_gbps;
   }
   if (probe_lds_check) j["ldsCheck"] = true;  // absent when off, likewise
+  if (probe_register_check) j["registerCheck"] = true;
   j["minHbmGBps"] = probe_min_hbm_gbps;
   j["minMfmaTflops"] = probe_min_mfma_tflops;
   j["recheckSeconds"] = probe_recheck_seconds;
@@ -354,6 +356,8 @@ std::vector<std::string> validate_mi355x(const Json& obj) {
     errs.push_back("spec.probe.hostLinkCheck: must be of type boolean");
   if (pr.contains("ldsCheck") && !pr["ldsCheck"].is_bool())
     errs.push_back("spec.probe.ldsCheck: must be of type boolean");
+  if (pr.contains("registerCheck") && !pr["registerCheck"].is_bool())
+    errs.push_back("spec.probe.registerCheck: must be of type boolean");
   if (pr.contains("hostLinkBytes")) {
     const int64_t b = pr["hostLinkBytes"].is_int() ? pr["hostLinkBytes"].as_int(0) : 0;
     if (b < (1LL << 20) || b > (1LL << 30)) errs.push_back("spec.probe.hostLinkBytes: must be within [1MiB, 1GiB]");

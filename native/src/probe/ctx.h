@@ -54,6 +54,16 @@ struct DeviceCtx {
   bool lds_clean = false;    // both sets hold their reset values
   uint32_t lds_runs = 0;     // the default "ldsSalt"
   void* lds_dump = nullptr;  // device copy of workgroup 0's LDS (mi355x_probe_lds with an image)
+  // register-file phase ("regCheck"): as the LDS phase's. regs_attr[i] is what the runtime says of
+  // rf_march<i>: registers per lane and workgroups per CU, asked once (0: not yet).
+  hipEvent_t regs_ev[2] = {};
+  unsigned long long* regs_cnt = nullptr;  // device, 2 sets
+  unsigned long long* regs_res = nullptr;  // pinned copy of the set a run used
+  int regs_set = 0;
+  bool regs_clean = false;
+  uint32_t regs_runs = 0;     // the default "regsSalt"
+  void* regs_dump = nullptr;  // device image uint32[4][512][64] (mi355x_probe_regs with an image)
+  int regs_attr[2][2] = {};
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;

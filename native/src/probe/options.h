@@ -30,6 +30,32 @@ inline long long opt_int(const char* json, const char* key, long long def) {
 
 inline bool opt_bool(const char* json, const char* key, bool def) { return opt_int(json, key, def) != 0; }
 
+// "key":[a, b, ...]: the first ``n`` integers of the array into ``out``; true when all n were there.
+inline bool opt_ints(const char* json, const char* key, long long* out, int n) {
+  if (!json) return false;
+  std::string pat = std::string("\"") + key + "\"";
+  const char* p = std::strstr(json, pat.c_str());
+  if (!p) return false;
+  p = std::strchr(p + pat.size(), ':');
+  if (!p) return false;
+  ++p;
+  while (*p == ' ') ++p;
+  if (*p != '[') return false;
+  ++p;
+  for (int i = 0; i < n; ++i) {
+    char* end = nullptr;
+    out[i] = std::strtoll(p, &end, 10);
+    if (end == p) return false;
+    p = end;
+    while (*p == ' ') ++p;
+    if (i + 1 < n) {
+      if (*p != ',') return false;
+      ++p;
+    }
+  }
+  return true;
+}
+
 constexpr long long kMaxPatterns = 4;
 
 // Default pattern (probe option "hbmPattern" selects per run, for in-process A/B). Measured on
@@ -216,6 +242,80 @@ struct Plan {
 
 }  // namespace lds
 
+namespace regs {
+
+// The vector register file of one gfx950 SIMD: v0..v255 and a0..a255 of every lane, numbered 0..511.
+constexpr int kRegistersPerLane = 512;
+constexpr int kLanes = 64;
+constexpr int kSimdsPerCU = 4;
+// One workgroup's registers as mi355x_probe_regs copies them out: uint32 [wave][register][lane].
+constexpr size_t kImageBytes = static_cast<size_t>(kSimdsPerCU) * kRegistersPerLane * kLanes * 4;
+// Workgroups per CU of the grid ("regsBlocksPerCU" selects per run): the oversubscription that makes
+// the dispatcher visit every CU, like the LDS phase's. A workgroup of this kernel needs a CU empty of
+// every other wave, so beside the HBM test it waits for that test's waves to drain. Measured on the
+// MI355X, two sweeps of 200 runs per factor (scripts/regs_claim_probe_cost.py,
+// profiles/regs_claim_probe_cost.json, regs_claim_probe_cost_run1.json): alone on the GPU every factor
+// from 1 up tested all 256 CUs on four SIMDs each in every run (kernel p50 0.043 ms at factor 1, 0.077 at 2,
+// linear above: 0.036 ms per workgroup per CU); inside the overlapped claim probe behind the MFMA phase factor 1
+// had one run of 400 that reached 251 CUs, 2, 4, 8 and 16 none; ahead of the MFMA phase no factor fell
+// short. The default is the smallest factor that never fell short at the default position.
+constexpr int kBlocksPerCU = 2;
+constexpr int kMaxBlocksPerCU = 64;
+// Where the phase sits on the MFMA stream ("regsFirst" selects per run): 0 behind the MFMA and
+// low-precision phases, 1 ahead of them. Same measurement, 40 alternating rounds at factor 2: behind
+// the MFMA phase the claim probe grows 0.764 -> 0.824 ms (+0.060; +0.126 at factor 4 in the run
+// before), ahead of it -> 0.880 ms (+0.115): ahead, the kernel's workgroups wait for CUs the first HBM
+// fill occupies (kernel 0.31 ms beside the probe against 0.16 behind, 0.077 alone), so unlike the LDS
+// phase this one is cheaper at the tail. Ahead wins only from factor 8 up (1.004 vs 1.031 ms).
+constexpr int kFirst = 0;
+
+// What one run of the phase does (options of mi355x_probe_run with "regCheck" and of mi355x_probe_regs).
+struct Plan {
+  bool on = false;  // false: the phase is off
+  int patterns = 2;
+  bool salt_given = false;  // else the phase takes the context's run counter
+  uint32_t salt = 0;        // "regsSalt", XORed into the seed
+  uint32_t seed = 0;        // 0x52454700 + dev, before the salt
+  int blocks_per_cu = kBlocksPerCU;
+  // test hooks, each off (-1) when out of range
+  int flip_u = -1, flip_lane = -1, flip_bit = -1;  // "injectRegFlip":[u, lane, bit]
+  int fault_simd = -1;                             // "injectRegFaultSimd": the flip only on that SIMD
+  int fault_xcc = -1;                              // "injectRegFaultXcc": the flip only on that XCD
+  int skip_u = -1;                                 // "injectRegSkip"
+  int dump_stage = 0;                              // "regsDumpStage" 1 | 2, only with a caller buffer
+  // the test instantiation of the kernel runs only when a hook or the dump asks for it
+  bool test_kernel() const { return flip_u >= 0 || skip_u >= 0 || dump_stage != 0; }
+  static Plan parse(const char* json, int dev) {
+    Plan pl;
+    pl.on = true;
+    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "regsPatterns", 2))));
+    const long long salt = opt_int(json, "regsSalt", -1);
+    pl.salt_given = salt >= 0;
+    pl.salt = pl.salt_given ? static_cast<uint32_t>(salt) : 0u;
+    pl.seed = 0x52454700u + static_cast<uint32_t>(dev);
+    pl.blocks_per_cu =
+        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "regsBlocksPerCU", kBlocksPerCU))));
+    long long f[3];
+    if (opt_ints(json, "injectRegFlip", f, 3) && f[0] >= 0 && f[0] < kRegistersPerLane && f[1] >= 0 && f[1] < kLanes &&
+        f[2] >= 0 && f[2] < 32) {
+      pl.flip_u = static_cast<int>(f[0]);
+      pl.flip_lane = static_cast<int>(f[1]);
+      pl.flip_bit = static_cast<int>(f[2]);
+    }
+    const long long simd = opt_int(json, "injectRegFaultSimd", -1);
+    pl.fault_simd = simd >= 0 && simd < kSimdsPerCU ? static_cast<int>(simd) : -1;
+    const long long xcc = opt_int(json, "injectRegFaultXcc", -1);
+    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
+    const long long skip = opt_int(json, "injectRegSkip", -1);
+    pl.skip_u = skip >= 0 && skip < kRegistersPerLane ? static_cast<int>(skip) : -1;
+    const long long stage = opt_int(json, "regsDumpStage", 0);
+    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    return pl;
+  }
+};
+
+}  // namespace regs
+
 // Where the GEMM fault hooks corrupt C (test hooks "injectGemmFaultRow" / "injectGemmFaultCol"):
 // -1 is the element the hooks always took, row n/3 and column n/5; any other value outside [0, n)
 // means no fault, like "injectFlipAtChunk".
@@ -271,6 +371,8 @@ struct ProbeOptions {
   bool host_link_on_mfma_stream = false;  // "hostLinkStream":1, for the A/B; only with overlap
   lds::Plan lds;                   // "ldsCheck"; n16 == 0: off, and none of its options is looked up
   bool lds_first = lds::kFirst == 1;  // "ldsFirst": 1 ahead of the MFMA phase on its stream, 0 behind it (A/B)
+  regs::Plan regs;                 // "regCheck"; !on: off, and none of its options is looked up
+  bool regs_first = regs::kFirst == 1;  // "regsFirst": as "ldsFirst"
 
   static ProbeOptions parse(const char* json, int dev = 0) {
     ProbeOptions o;
@@ -312,6 +414,11 @@ struct ProbeOptions {
       o.lds = lds::Plan::parse(json, dev);
       o.lds.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_lds
       o.lds_first = opt_int(json, "ldsFirst", lds::kFirst) == 1;
+    }
+    if (opt_bool(json, "regCheck", false)) {
+      o.regs = regs::Plan::parse(json, dev);
+      o.regs.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_regs
+      o.regs_first = opt_int(json, "regsFirst", regs::kFirst) == 1;
     }
     return o;
   }

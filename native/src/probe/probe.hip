@@ -32,6 +32,7 @@
 //   lowp.h           FP8 / MXFP8 / MXFP4 phase ("mfmaLowPrecision")
 //   hostlink.h       PCIe host-link phase ("hostLinkBytes")
 //   lds.h            per-CU LDS march and address test ("ldsCheck")
+//   regfile.h        per-SIMD vector register file march ("regCheck")
 //   ctx.h            per-device state and ensure_ctx(); peer.h the xGMI checks; sweep.h the HBM sweep
 #include <hip/hip_runtime.h>
 
@@ -53,6 +54,7 @@
 #include "lowp.h"
 #include "mfma_phase.h"
 #include "options.h"
+#include "regfile.h"
 #include "peer.h"
 #include "report.h"
 #include "sweep.h"
@@ -186,6 +188,8 @@ std::string run_probe(int dev, const char* opts) {
   }
   lds::Plan ld = o.lds;
   if (ld.n16) lds::ensure(ctx, false);
+  regs::Plan rg = o.regs;
+  if (rg.on) regs::ensure(ctx, rg.test_kernel(), false);
   ProbeReport rep;
   PhaseTimes& t = rep.phases;
   t.hbm_first = o.hbm_first;
@@ -203,7 +207,8 @@ std::string run_probe(int dev, const char* opts) {
   // enqueue: the HBM test on s, the MFMA phase and the low-precision phase behind it on s2, in
   // "hbmFirst" order; the host link after both, so it overlaps both. The LDS phase ("ldsCheck")
   // never gets a stream of its own: ahead of the MFMA phase on s2, where it overlaps the first HBM
-  // fill ("ldsFirst":0 behind it and the low-precision phase), or serial, last on the one stream
+  // fill ("ldsFirst":0 behind it and the low-precision phase), or serial, last on the one stream.
+  // The register-file phase ("regCheck", "regsFirst") takes the same places, behind the LDS phase
   auto t_run = std::chrono::steady_clock::now();
   reset_counters(ctx, o, cnt, s, s2);
   const lowp::Phase lp = lowp_phase(ctx, o, base, lay);
@@ -213,18 +218,27 @@ std::string run_probe(int dev, const char* opts) {
     lds::launch(ctx, s2, ld);
     lds_pending = false;
   };
+  bool regs_pending = rg.on;
+  auto enqueue_regs = [&](bool here) {
+    if (!regs_pending || !here) return;
+    regs::launch(ctx, s2, rg);
+    regs_pending = false;
+  };
   auto enqueue_mfma = [&](int when) {
     if (!o.mfma || o.hbm_first != when) return;
     enqueue_lds(o.overlap && o.lds_first);
+    enqueue_regs(o.overlap && o.regs_first);
     launch_mfma_phase(base, lay, o, ctx, s2);
     lowp::launch(s2, lp);
     enqueue_lds(o.overlap);
+    enqueue_regs(o.overlap);
   };
   const PatternPass pass = hbm_pass(ctx, o, dev, base, lay, n16);
   enqueue_mfma(0);
   enqueue_hbm(ctx, pass, o, cnt, [&] { enqueue_mfma(2); });
   enqueue_mfma(1);
   enqueue_lds(true);  // serial, or no MFMA phase to follow
+  enqueue_regs(true);
   if (hl.n16) hostlink::launch(ctx, hl_s, hl);
   t.launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
 
@@ -243,6 +257,11 @@ std::string run_probe(int dev, const char* opts) {
   if (ld.n16) {
     if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
     rep.lds = lds::finish(ctx, ld, o.require_all_cus);
+  }
+  rep.has_regs = rg.on;
+  if (rg.on) {
+    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
+    rep.regs = regs::finish(ctx, rg, o.require_all_cus);
   }
   rep.lowp = lowp::finish(lp, o.require_all_cus);
   t.mfma_wall_ms = o.mfma ? ms_since(t_run) : 0.0;
@@ -748,6 +767,25 @@ char* mi355x_probe_lds(int dev, const char* opts_json, void* image, size_t image
                             hipMemcpyDeviceToHost));
     // the block is the whole report, with the usual head
     return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + lds_block(r).substr(1);
+  });
+}
+
+char* mi355x_probe_regs(int dev, const char* opts_json, void* image, size_t image_bytes) {
+  if (!device_ok(dev)) return bad_device();
+  ProbeActive active;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded(device_head(dev), [&] {
+    regs::Plan pl = regs::Plan::parse(opts_json, dev);
+    if (!image || !image_bytes) pl.dump_stage = 0;
+    DeviceCtx& ctx = ensure_ctx(dev);
+    regs::ensure(ctx, pl.test_kernel(), pl.dump_stage != 0);
+    regs::launch(ctx, ctx.stream, pl);
+    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
+    const RegsResult r = regs::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
+    if (pl.dump_stage)
+      PROBE_CHECK(hipMemcpy(image, ctx.regs_dump, std::min<size_t>(image_bytes, regs::kImageBytes), hipMemcpyDeviceToHost));
+    // the block is the whole report, with the usual head
+    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + regs_block(r).substr(1);
   });
 }
 

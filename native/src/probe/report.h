@@ -175,6 +175,52 @@ inline std::string lds_block(const LdsResult& r) {
   return out + "}";
 }
 
+// The register-file phase: which CUs a workgroup marched all four SIMDs' vector register files of,
+// and what it found there. first_bad is (CU key << 32) | SIMD << 16 | register u << 6 | lane of the
+// lowest fault, all-ones = none. registers_per_lane / workgroups_per_cu are what the runtime says of
+// the kernel: anything but 512 and 1 and the kernel did not own the file it tested.
+struct RegsResult {
+  int registers_per_lane = 0, workgroups_per_cu = 0;
+  int patterns = 0;
+  uint32_t salt = 0;
+  unsigned long long workgroups = 0, simd_short = 0;
+  int expected = 0, tested = 0, verified = 0, bad_cus = 0;
+  int per_xcd[8] = {};  // verified
+  unsigned long long bad_bits = 0, first_bad = ~0ull;
+  float ms = 0;
+  bool require_all = true;  // "requireAllCUs"
+  int dump_cu = -1;         // mi355x_probe_regs with an image: the CU key of the dumped workgroup
+  int dump_simds[4] = {};   // ... and the SIMD each of its four waves ran on
+  bool exclusive() const { return registers_per_lane == 512 && workgroups_per_cu == 1; }
+  bool ok() const {
+    return bad_bits == 0 && exclusive() && simd_short == 0 && (!require_all || verified >= expected);
+  }
+};
+
+inline std::string regs_block(const RegsResult& r) {
+  std::string per = "[";
+  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
+  const bool none = r.first_bad == ~0ull;
+  auto field = [&](int shift, unsigned long long mask) {
+    return none ? std::string("null") : std::to_string((r.first_bad >> shift) & mask);
+  };
+  std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"registersPerLane\":" + std::to_string(r.registers_per_lane) +
+                    ",\"workgroupsPerCU\":" + std::to_string(r.workgroups_per_cu) +
+                    ",\"patterns\":" + std::to_string(r.patterns) + ",\"salt\":" + std::to_string(r.salt) +
+                    ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"cusTested\":" + std::to_string(r.tested) +
+                    ",\"cusVerified\":" + std::to_string(r.verified) + ",\"simdsTested\":" + std::to_string(4 * r.tested) +
+                    ",\"simdShort\":" + std::to_string(r.simd_short) + ",\"perXcd\":" + per + "]" +
+                    ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badBits\":" + std::to_string(r.bad_bits) +
+                    ",\"firstBadCU\":" + field(32, 0xFFFFFFFFull) + ",\"firstBadSimd\":" + field(16, 3) +
+                    ",\"firstBadRegister\":" + field(6, 511) + ",\"firstBadLane\":" + field(0, 63) +
+                    ",\"ms\":" + jnum(r.ms);
+  if (!r.exclusive()) out += ",\"error\":\"RegisterKernelNotExclusive\"";
+  if (r.dump_cu >= 0)
+    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
+           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  return out + "}";
+}
+
 // Host wall-clock of a probe's steps.
 struct PhaseTimes {
   bool arena_reused = false;
@@ -194,7 +240,7 @@ inline std::string phases_block(const PhaseTimes& t) {
 inline std::string device_head(int dev) { return "\"device\":" + std::to_string(dev); }
 
 // Everything mi355x_probe_run reports. "cus" only with the MFMA phase, "lowp" only with a dtype,
-// "hostLink" and "lds" only when asked for.
+// "hostLink", "lds" and "regs" only when asked for.
 struct ProbeReport {
   int dev = 0;
   std::string uuid, arch;
@@ -206,10 +252,13 @@ struct ProbeReport {
   HostLinkResult host_link;
   bool has_lds = false;
   LdsResult lds;
+  bool has_regs = false;
+  RegsResult regs;
   double total_ms = 0;
   PhaseTimes phases;
   bool passed() const {
-    bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok()) && (!has_lds || lds.ok());
+    bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok()) && (!has_lds || lds.ok()) &&
+              (!has_regs || regs.ok());
     for (const LowpResult& l : lowp) ok = ok && l.ok;
     return ok;
   }
@@ -230,6 +279,7 @@ inline std::string probe_report_open(const ProbeReport& r) {
   if (!r.lowp.empty()) out += ",\"lowp\":" + lowp_block(r.lowp);
   if (r.has_host_link) out += ",\"hostLink\":" + host_link_block(r.host_link);
   if (r.has_lds) out += ",\"lds\":" + lds_block(r.lds);
+  if (r.has_regs) out += ",\"regs\":" + regs_block(r.regs);
   out += ",\"ms\":" + jnum(r.total_ms);
   out += ",\"phases\":" + phases_block(r.phases);
   return out;

@@ -97,6 +97,8 @@ Json DeviceView::status_json() const {
       p["hostLinkGBps"] = probe.path("hostLink.GBps");
     if (probe["lds"].is_object())  // spec.probe.ldsCheck: the CUs whose whole LDS tested clean
       p["ldsVerifiedCUs"] = probe.path("lds.cusVerified");
+    if (probe["regs"].is_object())  // spec.probe.registerCheck: the CUs whose register files tested clean
+      p["regsVerifiedCUs"] = probe.path("regs.cusVerified");
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)

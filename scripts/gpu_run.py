@@ -105,6 +105,10 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # spec.probe.ldsCheck: the grid factor that reaches every CU and the phase's cost in the
         # claim probe (give lds_claim_probe_cost.py --parent-lib DIR by hand for the default-path A/B)
         "lds": [("lds_claim_probe_cost", [PY, "scripts/lds_claim_probe_cost.py"], 600, {})],
+        # spec.probe.registerCheck: the grid factor that reaches every CU, the cheaper position and the
+        # phase's cost in the claim probe (give regs_claim_probe_cost.py --parent-lib DIR
+        # --parent-lib-copy DIR2 by hand for the default-path A/B and its null pair)
+        "regs": [("regs_claim_probe_cost", [PY, "scripts/regs_claim_probe_cost.py"], 600, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],
