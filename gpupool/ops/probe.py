@@ -33,6 +33,10 @@ def lib() -> ctypes.CDLL:
             l.mi355x_probe_free.argtypes = [ctypes.c_void_p]
             l.mi355x_probe_peer.restype = ctypes.c_void_p
             l.mi355x_probe_peer.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
+            if hasattr(l, "mi355x_probe_peer_dump"):  # absent from a library built before it
+                l.mi355x_probe_peer_dump.restype = ctypes.c_void_p
+                l.mi355x_probe_peer_dump.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                                     ctypes.c_void_p, ctypes.c_size_t]
             if hasattr(l, "mi355x_probe_peer_ring"):  # absent from a library built before it
                 l.mi355x_probe_peer_ring.restype = ctypes.c_void_p
                 l.mi355x_probe_peer_ring.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int,
@@ -255,23 +259,39 @@ def regs(dev: int, patterns: int = 2, want_stage: int = 0, **hooks) -> dict:
     return res
 
 
-def peer(src: int, dst: int, nbytes: int = 64 << 20) -> dict:
+def peer(src: int, dst: int, nbytes: int = 64 << 20, want_bytes: int = 0, **hooks: int) -> dict:
     """xGMI peer check src -> dst: pattern written on src, hipMemcpyPeer over the link, every bit
-    verified on dst; reports GB/s. ``src == dst`` exercises the same path as a local copy."""
-    opts = json.dumps({"bytes": int(nbytes)})
-    return _take(lib().mi355x_probe_peer(src, dst, opts.encode()))
+    verified on dst; reports GB/s, "firstBadOffset" and the per-call "seed" it verified with.
+    ``src == dst`` exercises the same path as a local copy. ``want_bytes`` > 0: the first
+    ``min(want_bytes, tested bytes)`` of the destination buffer after the verify come back under
+    "data" (bytes; ``gpupool.ops.hostlink.pattern_bytes`` with the reported seed is their numpy
+    twin). ``hooks`` (test hooks): injectFlipAtChunk=i / injectBitFlips=k corrupt the destination
+    between the copy and the verify, skipCopy=1 leaves the copy out."""
+    opts = json.dumps({"bytes": int(nbytes), **{k: int(v) for k, v in hooks.items()}}).encode()
+    if want_bytes <= 0:
+        return _take(lib().mi355x_probe_peer(src, dst, opts))
+    if not hasattr(lib(), "mi355x_probe_peer_dump"):
+        raise RuntimeError("libmi355x_probe.so predates the peer check's dump: rebuild it")
+    n = int(want_bytes)
+    buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_peer_dump(src, dst, opts, buf, n))
+    if "bytes" in res:
+        res["data"] = buf.raw[:min(n, int(res["bytes"]))]
+    return res
 
 
-def peer_ring(ordinals: list[int], nbytes: int = 64 << 20) -> dict:
+def peer_ring(ordinals: list[int], nbytes: int = 64 << 20, **hooks: int) -> dict:
     """The xGMI ring in one call: link i copies ordinals[i] -> ordinals[i+1] (wrapping), every link
-    concurrently, then each receiver verifies every bit. -> {"links": [...], "passed"}."""
+    concurrently, then each receiver verifies every bit. -> {"links": [...], "passed"}. ``hooks``
+    (test hooks): injectFlipAtChunk=i / injectBitFlips=k corrupt the receive window of link
+    injectLink=j (default 0) ahead of its verify, skipCopy=1 leaves every link's copy out."""
     n = len(ordinals)
     if n < 2:
         raise ValueError("a ring needs at least 2 entries")
     if not hasattr(lib(), "mi355x_probe_peer_ring"):
         raise RuntimeError("libmi355x_probe.so predates the ring check: rebuild it")
     arr = (ctypes.c_int * n)(*[int(o) for o in ordinals])
-    opts = json.dumps({"bytes": int(nbytes)})
+    opts = json.dumps({"bytes": int(nbytes), **{k: int(v) for k, v in hooks.items()}})
     return _take(lib().mi355x_probe_peer_ring(arr, n, opts.encode()))
 
 
@@ -296,7 +316,10 @@ def hbm_sweep(dev: int, offset: int, nbytes: int = 16 << 30, reserve: int = 4 <<
               keep: bool = False, **test_hooks: int) -> dict:
     """Pattern-test HBM window [offset, offset+nbytes) of a buffer spanning all free HBM minus
     ``reserve`` (the rotating sweep that covers the whole 288 GB over successive calls). With
-    ``keep`` the big buffer stays allocated for the next window (free it with sweep_release)."""
+    ``keep`` the big buffer stays allocated for the next window (free it with sweep_release).
+    ``test_hooks``: injectBitFlips=k (spread over the window's first piece), injectFlipAtChunk=i
+    (bit 0 of 16-byte chunk i counted from the window's start, in whichever 1 GiB chunk of the
+    buffer holds it; past the window: no flip)."""
     opts = json.dumps({"offset": int(offset), "bytes": int(nbytes), "reserve": int(reserve),
                        "keep": bool(keep), **{k: int(v) for k, v in test_hooks.items()}})
     return _take(lib().mi355x_probe_hbm_sweep(dev, opts.encode()))

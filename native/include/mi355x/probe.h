@@ -138,21 +138,46 @@ char* mi355x_probe_host_link(int device, const char* opts_json, void* io, size_t
 void mi355x_probe_host_link_geometry(int* grid, int* threads, int* unroll);
 /* xGMI peer check: src writes a pattern, copies it to dst over the peer link
  * (hipMemcpyPeerAsync after hipDeviceEnablePeerAccess), dst verifies every bit.
- * opts: {"bytes":268435456}. src == dst runs the same path as a local device copy.
- * -> {"src","dst","canAccessPeer":bool,"passed":bool,"badBits","GBps","ms"} */
+ * opts: {"bytes":268435456} (at least 1 MiB, rounded down to 16). src == dst runs the same path as a
+ * local device copy.
+ * -> {"src","dst","canAccessPeer":bool,"passed":bool,"badBits","firstBadOffset","bytes","GBps","ms",
+ *     "seed"}
+ * firstBadOffset: the byte offset of the lowest faulting 16-byte chunk of the destination, or null.
+ * seed: what this call filled and verified with — the link's base seed mixed with a per-call nonce
+ * (a process-wide counter), so data that an earlier call left in the destination's memory never
+ * verifies as this call's. The pattern is the cheap one of the HBM test (pattern16<1>, polarity 0).
+ * Test hooks, all on the receiving buffer between the copy and the verify: "injectFlipAtChunk":i
+ * (bit 0 of 16-byte chunk i; i >= bytes / 16: no flip), "injectBitFlips":k (0..4096, spread as in
+ * mi355x_probe_run); and "skipCopy":1 — the copy is not enqueued, everything else (fill, events,
+ * verify) runs, so the check must fail on whatever the destination held. */
 char* mi355x_probe_peer(int src, int dst, const char* opts_json);
+/* The same check; io may be NULL: after the verify the first min(io_bytes, tested bytes) of the
+ * destination buffer are copied into it (what arrived, hooks included). */
+char* mi355x_probe_peer_dump(int src, int dst, const char* opts_json, void* io, size_t io_bytes);
 /* The whole ring at once: link i copies devs[i] -> devs[(i+1) % n], all links concurrently (each
  * GPU pair of an MI355X node has its own xGMI link), then every receiver verifies. Send / receive
  * windows are kept between calls and freed with the idle arena. A device may repeat ([0, 0] on a
  * 1-GPU box runs local copies through the same path). opts: {"bytes":67108864}
- * -> {"bytes","links":[{"src","dst","canAccessPeer","passed","badBits","bytes","GBps","ms"}],
- *     "passed":bool} */
+ * -> {"bytes","links":[{"src","dst","canAccessPeer","passed","badBits","firstBadOffset","bytes","GBps",
+ *                       "ms","seed"}],"passed":bool}
+ * One pattern per source device and call: every link's seed mixes the call's nonce as above, because
+ * the kept receive windows still hold the previous ring's data. Test hooks as for mi355x_probe_peer;
+ * the two flip hooks strike the receive window of link "injectLink":j (default 0) ahead of that
+ * link's verify (links that share a receive window — a repeated device — and are verified after it
+ * see the flip too); "skipCopy":1 skips every link's copy. */
 char* mi355x_probe_peer_ring(const int* devs, int n, const char* opts_json);
 /* One window of the rotating HBM sweep: a buffer of all free HBM minus "reserve" bytes is
  * allocated (kept across calls while "keep" is true; released by mi355x_probe_sweep_release) and
  * [offset, offset+bytes) of it is pattern-tested in both polarities.
  * opts: {"offset":0,"bytes":17179869184,"reserve":4294967296,"keep":false,"injectBitFlips":0}
- * -> {"passed","offset","bytes","span","badBits","firstBadOffset","GBps","ms","allocMs"} */
+ * -> {"passed","offset","bytes","span","badBits","firstBadOffset","GBps","ms","allocMs"}
+ * offset wraps modulo span and is rounded down to 16; bytes (at least 1 MiB) is clipped to the end of
+ * the span and rounded down to 16; both come back as tested. The buffer is made of 1 GiB chunks (the
+ * last one shorter): a window that straddles them is tested piece by piece, each piece with a seed of
+ * its own. firstBadOffset is a byte offset into the buffer (not into the window), or null. Test hooks,
+ * both after the first fill: "injectBitFlips":k (0..4096, spread over the window's first piece),
+ * "injectFlipAtChunk":i (bit 0 of the window's 16-byte chunk i, in whichever piece holds it; past the
+ * window: no flip). */
 char* mi355x_probe_hbm_sweep(int device, const char* opts_json);
 /* Allocate / free the sweep buffer without holding the device's probe lock (allocating ~282 GiB
  * takes ~0.4 s and freeing it ~2.9 s on MI355X: a claim-time probe must never wait for either).

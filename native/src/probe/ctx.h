@@ -18,7 +18,7 @@
 namespace {
 
 struct SweepBuf {
-  std::vector<void*> chunks;  // kSweepChunk bytes each, the last one possibly shorter (sweep.h)
+  std::vector<void*> chunks;  // kSweepChunk bytes each, the last one possibly shorter (sweep_window.h)
   uint64_t span = 0;
   bool empty() const { return chunks.empty(); }
 };

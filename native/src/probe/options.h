@@ -441,13 +441,44 @@ inline uint64_t peer_bytes(const char* json, long long def) {
   return static_cast<uint64_t>(std::max(1LL << 20, opt_int(json, "bytes", def)));
 }
 
+// The seed one call of a peer check fills and verifies a link with: the link's fixed base seed mixed
+// with a per-call nonce (peer.h takes it from a process-wide counter). The receive windows outlive a
+// call (the ring keeps them, the pair check's fresh allocation usually lands on the last one's
+// memory), and with a fixed seed they already hold exactly what the next call expects: a copy that
+// delivered nothing would verify. The odd multiplier makes nonce -> seed a bijection for one base,
+// and the XOR keeps the seeds of two bases apart within one call.
+inline uint32_t peer_call_seed(uint32_t base, uint32_t nonce) { return base ^ (nonce * 0x9E3779B1u); }
+
+// mi355x_probe_peer (default 256 MiB) and mi355x_probe_peer_ring (64 MiB): "bytes" and the test hooks.
+struct PeerOptions {
+  uint64_t bytes = 0;           // at least 1 MiB; the checks round it down to whole 16-byte chunks
+  long long inject_chunk = -1;  // test hook "injectFlipAtChunk": bit 0 of that chunk of the receiving window
+  int inject_flips = 0;         // test hook "injectBitFlips", 0..4096, spread over the receiving window
+  int inject_link = 0;          // "injectLink": the ring link the two hooks strike (a pair check ignores it)
+  bool skip_copy = false;       // test hook "skipCopy": no link's copy is enqueued, everything else runs
+  static PeerOptions parse(const char* json, long long def_bytes) {
+    PeerOptions o;
+    o.bytes = peer_bytes(json, def_bytes);
+    o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
+    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    o.inject_link = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectLink", 0))));
+    o.skip_copy = opt_bool(json, "skipCopy", false);
+    return o;
+  }
+  // the chunk of an n16-chunk window to flip, or -1: none (out of range: no flip)
+  long long flip_chunk(uint64_t n16) const {
+    return inject_chunk >= 0 && static_cast<uint64_t>(inject_chunk) < n16 ? inject_chunk : -1;
+  }
+};
+
 // mi355x_probe_hbm_sweep.
 struct SweepOptions {
   uint64_t bytes = 16ull << 30;   // window, at least 1 MiB
   uint64_t reserve = 4ull << 30;  // free HBM left alone when the call has to allocate the buffer
   uint64_t offset = 0;
   bool keep = false;
-  int inject_flips = 0;  // test hook, 0..4096
+  int inject_flips = 0;  // test hook, 0..4096, in the window's first piece
+  long long inject_chunk = -1;  // test hook "injectFlipAtChunk": bit 0 of that 16-byte chunk of the window
   static SweepOptions parse(const char* json) {
     SweepOptions o;
     o.bytes = static_cast<uint64_t>(std::max(1LL << 20, opt_int(json, "bytes", 16LL << 30)));
@@ -455,6 +486,7 @@ struct SweepOptions {
     o.offset = static_cast<uint64_t>(std::max(0LL, opt_int(json, "offset", 0)));
     o.keep = opt_bool(json, "keep", false);
     o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
     return o;
   }
 };

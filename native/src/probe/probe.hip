@@ -34,6 +34,7 @@
 //   lds.h            per-CU LDS march and address test ("ldsCheck")
 //   regfile.h        per-SIMD vector register file march ("regCheck")
 //   ctx.h            per-device state and ensure_ctx(); peer.h the xGMI checks; sweep.h the HBM sweep
+//   sweep_window.h   a sweep window split over the buffer's chunks (pure host, unit-tested)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -451,13 +452,17 @@ char* mi355x_probe_run(int dev, const char* opts_json) {
   return guarded(device_head(dev), [&] { return run_probe(dev, opts_json); });
 }
 
-char* mi355x_probe_peer(int src, int dst, const char* opts_json) {
+char* mi355x_probe_peer_dump(int src, int dst, const char* opts_json, void* io, size_t io_bytes) {
   if (!device_ok(src) || !device_ok(dst)) return bad_device();
   // both devices' probe locks, in index order (no deadlock against a concurrent pair)
   std::lock_guard<std::mutex> a(device_mutex(std::min(src, dst)));
   std::unique_lock<std::mutex> b;
   if (src != dst) b = std::unique_lock<std::mutex>(device_mutex(std::max(src, dst)));
-  return guarded(link_head(src, dst), [&] { return run_peer(src, dst, opts_json); });
+  return guarded(link_head(src, dst), [&] { return run_peer(src, dst, opts_json, io, io_bytes); });
+}
+
+char* mi355x_probe_peer(int src, int dst, const char* opts_json) {
+  return mi355x_probe_peer_dump(src, dst, opts_json, nullptr, 0);
 }
 
 char* mi355x_probe_peer_ring(const int* devs, int n, const char* opts_json) {

@@ -297,9 +297,10 @@ inline std::string error_report(const std::string& head, const std::string& what
 struct PeerLink {
   int src = 0, dst = 0;
   std::string error;  // non-empty: no peer access
-  unsigned long long bad_bits = 0;
+  unsigned long long bad_bits = 0, first_bad = ~0ull;  // first_bad: a 16-byte chunk of the receiving window
   uint64_t bytes = 0;
   float ms = 0;
+  uint32_t seed = 0;  // what the link was verified with (peer_call_seed: it differs from call to call)
   bool ok() const { return error.empty() && bad_bits == 0; }
 };
 
@@ -308,8 +309,9 @@ inline std::string peer_link_block(const PeerLink& l) {
     return "{" + link_head(l.src, l.dst) + ",\"canAccessPeer\":false,\"passed\":false,\"error\":" + jstr(l.error) + "}";
   const double gbps = l.ms > 0 ? static_cast<double>(l.bytes) / (l.ms * 1e-3) / 1e9 : 0.0;
   return "{" + link_head(l.src, l.dst) + ",\"canAccessPeer\":true,\"passed\":" + jbool(l.bad_bits == 0) +
-         ",\"badBits\":" + std::to_string(l.bad_bits) + ",\"bytes\":" + std::to_string(l.bytes) +
-         ",\"GBps\":" + jnum(gbps) + ",\"ms\":" + jnum(l.ms) + "}";
+         ",\"badBits\":" + std::to_string(l.bad_bits) + ",\"firstBadOffset\":" + joffset(l.first_bad) +
+         ",\"bytes\":" + std::to_string(l.bytes) + ",\"GBps\":" + jnum(gbps) + ",\"ms\":" + jnum(l.ms) +
+         ",\"seed\":" + std::to_string(l.seed) + "}";
 }
 
 inline std::string peer_ring_report(uint64_t bytes, const std::vector<PeerLink>& links) {

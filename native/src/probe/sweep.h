@@ -14,17 +14,9 @@
 #include "hbm.h"
 #include "options.h"
 #include "report.h"
+#include "sweep_window.h"  // kSweepChunk and how a window splits over the chunks
 
 namespace {
-
-// The HBM sweep buffer is allocated as kSweepChunk pieces, not one ~282 GiB allocation: freeing
-// one huge mapping held the process's address-space lock for ~2.5 s, and every thread of the agent
-// that mapped memory meanwhile (a thread start, a large malloc) stalled behind it — a claim issued
-// right after a scrub waited 2.46 s (profiles/r2o_scrub_claim_diag.txt). Per chunk the stall is
-// bounded by one chunk's unmap. 1 GiB: VRAM that an earlier process used is cleared as it is mapped
-// again, at ~35 GB/s — 121 ms per 4 GiB chunk on a box whose last tenant left 90 GiB dirty
-// (profiles/r4r_sweep_chunks.txt) — and a claim-time probe that arrives mid-chunk waits for it.
-constexpr uint64_t kSweepChunk = 1ull << 30;
 
 // All free HBM minus ``reserve``, 2 MiB granular, as kSweepChunk pieces. Measured on MI355X
 // (profiles/r2h_sweep_claim_diag.txt): ~0.2 s to allocate ~282 GiB of fresh VRAM, ~6 s once the
@@ -104,14 +96,18 @@ inline void sweep_free(SweepBuf& b, int yield_dev = -1) {
 }
 
 // One piece of a window inside one chunk: both polarities, one sync. Adds its time and counters to
-// ``r``; ``chunk0``: the piece's first 16-byte chunk counted from the window's start.
-inline void sweep_piece(DeviceCtx& ctx, const PatternPass& pass, int inject_flips, uint64_t chunk0, SweepResult* r) {
+// ``r``; ``chunk0``: the piece's first 16-byte chunk counted from the window's start. Test hooks,
+// both after the first fill: ``inject_flips`` bits spread over the piece, bit 0 of the piece's
+// chunk ``flip_at`` (-1: none).
+inline void sweep_piece(DeviceCtx& ctx, const PatternPass& pass, int inject_flips, long long flip_at, uint64_t chunk0,
+                        SweepResult* r) {
   unsigned long long* cnt = ctx.sweep_cnt;
   memset_pairs(pass.s, cnt, 4, 2);
   PROBE_CHECK(hipEventRecord(ctx.ev[0], pass.s));
   for (int pi = 0; pi < 2; ++pi) {
     pass.fill(pi);
     if (pi == 0 && inject_flips > 0) pass.inject_flips(inject_flips);
+    if (pi == 0 && flip_at >= 0) pass.inject_flip_at(static_cast<uint64_t>(flip_at));
     pass.verify(pi, cnt + 2 * pi);
   }
   PROBE_CHECK(hipEventRecord(ctx.ev[1], pass.s));
@@ -140,27 +136,26 @@ inline std::string run_sweep(int dev, const char* opts) {
     ctx.sweep = sweep_alloc_raw(o.reserve);
     r.alloc_ms = ms_since(t0);
   }
-  const uint64_t span = r.span = ctx.sweep.span;
-  const uint64_t offset = r.offset = (o.offset % span) & ~static_cast<uint64_t>(15);
-  const uint64_t bytes = r.bytes = std::min<uint64_t>(o.bytes, span - offset) & ~static_cast<uint64_t>(15);
+  r.span = ctx.sweep.span;
+  const SweepWindow w = sweep_window(ctx.sweep.span, kSweepChunk, o.offset, o.bytes);
+  r.offset = w.offset;
+  r.bytes = w.bytes;
   if (!ctx.sweep_cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx.sweep_cnt), 4 * sizeof(unsigned long long)));
   const int cus = ctx.prop.multiProcessorCount;
   // the window may straddle chunks: test it piece by piece (both polarities per piece)
-  for (uint64_t pos = offset; pos < offset + bytes;) {
-    const size_t ci = static_cast<size_t>(pos / kSweepChunk);
-    const uint64_t in = pos % kSweepChunk;
-    const uint64_t clen = std::min<uint64_t>(kSweepChunk, span - ci * kSweepChunk);
-    const uint64_t n = std::min<uint64_t>(offset + bytes - pos, clen - in) & ~static_cast<uint64_t>(15);
-    if (n == 0) break;
+  for (const SweepPiece& p : w.pieces) {
     PatternPass pass;
     pass.s = ctx.stream;
-    pass.buf = reinterpret_cast<u32x4*>(static_cast<char*>(ctx.sweep.chunks[ci]) + in);
-    pass.n16 = n / 16;
-    pass.seed = 0x5CAB0000u ^ static_cast<uint32_t>(pos >> 20);
+    pass.buf = reinterpret_cast<u32x4*>(static_cast<char*>(ctx.sweep.chunks[p.chunk]) + p.in);
+    pass.n16 = p.bytes / 16;
+    pass.seed = p.seed;
     pass.fill_grid = hbm_grid(cus, kHbmFillBlocksPerCU, pass.n16);
     pass.verify_grid = hbm_grid(cus, kHbmVerifyBlocksPerCU, pass.n16);
-    sweep_piece(ctx, pass, pos == offset ? o.inject_flips : 0, (pos - offset) / 16, &r);
-    pos += n;
+    // "injectFlipAtChunk" counts from the window's start and strikes the piece that holds that chunk
+    const bool flip_here = o.inject_chunk >= 0 && static_cast<uint64_t>(o.inject_chunk) >= p.first16 &&
+                           static_cast<uint64_t>(o.inject_chunk) - p.first16 < pass.n16;
+    sweep_piece(ctx, pass, p.first16 == 0 ? o.inject_flips : 0,
+                flip_here ? o.inject_chunk - static_cast<long long>(p.first16) : -1, p.first16, &r);
   }
   if (!o.keep) sweep_free(ctx.sweep);
   return sweep_report(r);

@@ -1,6 +1,8 @@
 // The probe's options (native/src/probe/options.h): defaults, clamps, fall-backs and the strings
 // the project itself sends, against opt_int key by key.
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../src/probe/options.h"
 #include "gpupool/api.h"
@@ -152,9 +154,67 @@ TEST(probe_options_other_entry_points) {
   EXPECT_EQ(s.offset, 0ull);
   EXPECT_TRUE(s.keep);
   EXPECT_EQ(s.inject_flips, 4096);
+  EXPECT_EQ(d.inject_chunk, -1LL);
+  EXPECT_EQ(s.inject_chunk, -1LL);
+  EXPECT_EQ(SweepOptions::parse(R"({"injectFlipAtChunk": 65536})").inject_chunk, 65536LL);
   const HostLinkOptions h = HostLinkOptions::parse(R"({"preload":true,"hostLinkBytes":64})");
   EXPECT_TRUE(h.preload);
   EXPECT_EQ(h.bytes, 64ull);
+}
+
+TEST(probe_options_peer) {
+  // defaults: the entry point's size, no hook
+  for (long long def : {256LL << 20, 64LL << 20}) {
+    const PeerOptions d = PeerOptions::parse(nullptr, def);
+    EXPECT_EQ(d.bytes, static_cast<uint64_t>(def));
+    EXPECT_EQ(d.inject_chunk, -1LL);
+    EXPECT_EQ(d.inject_flips, 0);
+    EXPECT_EQ(d.inject_link, 0);
+    EXPECT_TRUE(!d.skip_copy);
+    EXPECT_EQ(d.flip_chunk(65536), -1LL);
+  }
+  // what probe.peer / probe.peer_ring send
+  const PeerOptions o = PeerOptions::parse(
+      R"({"bytes": 4194312, "injectFlipAtChunk": 262143, "injectBitFlips": 37, "injectLink": 2, "skipCopy": 1})", 64LL << 20);
+  EXPECT_EQ(o.bytes, 4194312ull);  // the checks round down to 16, not the parser
+  EXPECT_EQ(o.bytes, peer_bytes(R"({"bytes": 4194312})", 64LL << 20));
+  EXPECT_EQ(o.inject_chunk, 262143LL);
+  EXPECT_EQ(o.inject_flips, 37);
+  EXPECT_EQ(o.inject_link, 2);
+  EXPECT_TRUE(o.skip_copy);
+  // the flip is in range only below n16: the last chunk yes, one past it and anything negative no
+  EXPECT_EQ(o.flip_chunk(262144), 262143LL);
+  EXPECT_EQ(o.flip_chunk(262143), -1LL);
+  EXPECT_EQ(PeerOptions::parse(R"({"injectFlipAtChunk":0})", 1 << 20).flip_chunk(1), 0LL);
+  EXPECT_EQ(PeerOptions::parse(R"({"injectFlipAtChunk":-7})", 1 << 20).flip_chunk(65536), -1LL);
+  // clamps
+  const PeerOptions c = PeerOptions::parse(R"({"bytes":16,"injectBitFlips":9999,"injectLink":-3,"skipCopy":false})", 64LL << 20);
+  EXPECT_EQ(c.bytes, 1ull << 20);
+  EXPECT_EQ(c.inject_flips, 4096);
+  EXPECT_EQ(c.inject_link, 0);
+  EXPECT_TRUE(!c.skip_copy);
+  EXPECT_EQ(PeerOptions::parse(R"({"injectBitFlips":-1})", 1 << 20).inject_flips, 0);
+  EXPECT_TRUE(PeerOptions::parse(R"({"skipCopy":true})", 1 << 20).skip_copy);
+}
+
+TEST(probe_peer_call_seed) {
+  const uint32_t pair01 = 0x5EED0000u + 1, ring0 = 0x5EED0000u, ring1 = 0x5EED0000u + 0x9E37u;
+  // one base: no two of many consecutive calls share a seed, and none equals the bare base
+  for (uint32_t base : {pair01, ring0, ring1}) {
+    std::vector<uint32_t> seen;
+    for (uint32_t nonce = 1; nonce <= 4096; ++nonce) seen.push_back(peer_call_seed(base, nonce));
+    for (uint32_t s : seen) EXPECT_TRUE(s != base);
+    std::sort(seen.begin(), seen.end());
+    EXPECT_TRUE(std::adjacent_find(seen.begin(), seen.end()) == seen.end());
+  }
+  // one call: the devices of a ring keep distinct seeds (a window copied from the wrong source fails)
+  for (uint32_t nonce : {1u, 2u, 0x80000000u, 0xFFFFFFFFu})
+    for (uint32_t a = 0; a < 64; ++a)
+      for (uint32_t b = a + 1; b < 64; ++b)
+        EXPECT_TRUE(peer_call_seed(0x5EED0000u + a * 0x9E37u, nonce) != peer_call_seed(0x5EED0000u + b * 0x9E37u, nonce));
+  // the counter wrapping after 2^32 calls is the only repeat
+  EXPECT_EQ(peer_call_seed(ring0, 0), ring0);
+  EXPECT_EQ(peer_call_seed(ring0, 1), ring0 ^ 0x9E3779B1u);
 }
 
 // Every field against the opt_int expression it replaces in run_probe, on a string the project sends.

@@ -165,8 +165,16 @@ TEST(probe_report_error_peer_and_sweep) {
   ok.dst = 1;
   ok.bytes = 1048576;
   ok.ms = 0.5f;
-  const S a = R"({"src":0,"dst":1,"canAccessPeer":true,"passed":true,"badBits":0,"bytes":1048576,"GBps":2.09715,"ms":0.5})";
+  ok.seed = 0xFFFFFFFFu;
+  const S a = R"({"src":0,"dst":1,"canAccessPeer":true,"passed":true,"badBits":0,"firstBadOffset":null,"bytes":1048576,"GBps":2.09715,"ms":0.5,"seed":4294967295})";
   EXPECT_EQ(peer_link_block(ok), a);
+  PeerLink bad = ok;
+  bad.bad_bits = 3;
+  bad.first_bad = 65535;  // a chunk index: reported as its byte offset
+  bad.seed = 7;
+  const S c = R"({"src":0,"dst":1,"canAccessPeer":true,"passed":false,"badBits":3,"firstBadOffset":1048560,"bytes":1048576,"GBps":2.09715,"ms":0.5,"seed":7})";
+  EXPECT_EQ(peer_link_block(bad), c);
+  EXPECT_EQ(peer_ring_report(1048576, {ok, bad}), "{\"bytes\":1048576,\"links\":[" + a + "," + c + "],\"passed\":false}");
   PeerLink no = ok;
   no.src = 1;
   no.dst = 0;

@@ -26,7 +26,7 @@ HOST_LINK = ["ok", "bytes", "patterns", "seed", "badBits", "firstBadOffset", "ho
 PHASES = ["arenaReused", "setupMs", "allocMs", "launchMs", "hbmFirst", "hbmWallMs", "mfmaWallMs", "freeMs"]
 SWEEP = ["device", "passed", "offset", "bytes", "span", "badBits", "firstBadOffset", "GBps", "ms", "allocMs"]
 RING = ["bytes", "links", "passed"]
-LINK = ["src", "dst", "canAccessPeer", "passed", "badBits", "bytes", "GBps", "ms"]
+LINK = ["src", "dst", "canAccessPeer", "passed", "badBits", "firstBadOffset", "bytes", "GBps", "ms", "seed"]
 
 
 @pytest.fixture(scope="module")
