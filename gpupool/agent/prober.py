@@ -241,6 +241,7 @@ class Prober:
             if opts.get("hostLinkCheck") else 0
         lds = bool(opts.get("ldsCheck"))  # spec.probe.ldsCheck: the per-CU LDS phase
         regs = bool(opts.get("registerCheck"))  # spec.probe.registerCheck: the register-file phase
+        alu = bool(opts.get("aluCheck"))  # spec.probe.aluCheck: the vector-ALU phase
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -262,6 +263,8 @@ class Prober:
                 args["ldsCheck"] = True
             if regs:
                 args["registerCheck"] = True
+            if alu:
+                args["aluCheck"] = True
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -276,13 +279,15 @@ class Prober:
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
                                     overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
                                     host_link_bytes=hostlink, **({"lds_check": True} if lds else {}),
-                                    **({"reg_check": True} if regs else {}))
+                                    **({"reg_check": True} if regs else {}),
+                                    **({"alu_check": True} if alu else {}))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
                     (["--low-precision", ",".join(lowp)] if lowp else []) + \
                     (["--host-link-bytes", str(hostlink)] if hostlink else []) + \
-                    (["--lds-check"] if lds else []) + (["--register-check"] if regs else [])
+                    (["--lds-check"] if lds else []) + (["--register-check"] if regs else []) + \
+                    (["--alu-check"] if alu else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -333,7 +338,9 @@ class Prober:
         bits flipped on the PCIe link and the host's sample of its own memory; for
         spec.probe.ldsCheck the bits flipped in a CU's LDS, or the CUs no workgroup reached; for
         spec.probe.registerCheck the bits flipped in a SIMD's vector register file, the CUs not
-        covered, or a kernel that did not own the file it tested)."""
+        covered, or a kernel that did not own the file it tested; for spec.probe.aluCheck the waves
+        whose vector-ALU digests differ from the host's, the waves that disagree on the
+        transcendental digest, or the SIMDs not covered)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -398,6 +405,24 @@ class Prober:
                     (expected and regs.get("cusTested", 0) < expected):
                 why.append(f"RegisterCoverageShort: {regs.get('cusVerified')}/{expected or '?'} CUs verified, "
                            f"per XCD {regs.get('perXcd')}, {regs.get('simdShort')} workgroup(s) on fewer than 4 SIMDs")
+        alu = res.get("alu") or {}
+        if alu and not alu.get("ok", True):
+            if alu.get("badWaves"):
+                k = int(alu.get("firstBadCU") or 0)  # the 11-bit key: xcc[10:8] se[7:5] sh[4] cu[3:0]
+                why.append(f"ALUResultMismatch({alu.get('firstBadGroup')}): {alu['badWaves']} wave(s) on "
+                           f"{alu.get('badCUs')} CU(s), first on CU "
+                           f"{k >> 8}/{(k >> 5) & 7}/{(k >> 4) & 1}/{k & 15} SIMD {alu.get('firstBadSimd')} "
+                           f"lane {alu.get('firstBadLane')}")
+            if alu.get("splitWaves"):
+                k = int(alu.get("suspectCU") or 0)
+                why.append(f"ALUConsensusSplit: {alu['splitWaves']} of {alu.get('waves')} wave(s) disagree on the "
+                           f"transcendental digest, suspect CU {k >> 8}/{(k >> 5) & 7}/{(k >> 4) & 1}/{k & 15} "
+                           f"SIMD {alu.get('suspectSimd')}")
+            # SIMDs no wave covered; without the above nothing else fails the block
+            expected = cus.get("expected")
+            if not (alu.get("badWaves") or alu.get("splitWaves")) or \
+                    (expected and alu.get("simdsTested", 0) < 4 * expected):
+                why.append(f"ALUCoverageShort: {alu.get('simdsVerified')}/{4 * expected if expected else '?'} SIMDs")
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

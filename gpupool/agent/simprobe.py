@@ -28,6 +28,12 @@ SIM_LDS_MS = 0.2
 # regs::kBlocksPerCU, profiles/regs_claim_probe_cost.json)
 SIM_REGS_BLOCKS_PER_CU = 2
 SIM_REGS_MS = 0.15
+# the vector-ALU phase's grid factor, step count and kernel time (native/src/probe/options.h
+# alu::kBlocksPerCU, alu::kIters, profiles/alu_claim_probe_cost.json) and the digest it reports
+SIM_ALU_BLOCKS_PER_CU = 1
+SIM_ALU_ITERS = 64
+SIM_ALU_MS = 0.14
+SIM_ALU_TRANS_DIGEST = "0" * 16
 SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
@@ -114,6 +120,29 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                        "badCUs": bad, "badBits": bad, "firstBadCU": 0 if bad else None,
                        "firstBadSimd": 0 if bad else None, "firstBadRegister": 17 if bad else None,
                        "firstBadLane": 0 if bad else None, "ms": SIM_REGS_MS}
+        if bad:
+            res["passed"] = False
+    # spec.probe.aluCheck: the block the gfx950 probe reports; the overlay's ``aluFault: n`` marks n CUs
+    # bad, every wave on them with one lane off the host's digest, the first on the CU with key 0,
+    # SIMD 0, group f32, lane 0
+    if opts.get("aluCheck"):
+        cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
+        bad = min(cus, int(fault(dev, "aluFault") or 0))
+        per = [4 * (cus // 8 + (1 if x < cus % 8 else 0)) for x in range(8)]
+        left = 4 * bad
+        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
+            take = min(left, per[x])
+            per[x] -= take
+            left -= take
+        wg = SIM_ALU_BLOCKS_PER_CU * cus
+        res["alu"] = {"ok": bad == 0, "iters": SIM_ALU_ITERS, "workgroups": wg, "waves": 4 * wg,
+                      "wavesPerSimd": [wg] * 4, "simdsTested": 4 * cus, "simdsVerified": 4 * (cus - bad),
+                      "cusVerified": cus - bad, "perXcd": per, "badWaves": 4 * SIM_ALU_BLOCKS_PER_CU * bad,
+                      "badLanes": 4 * SIM_ALU_BLOCKS_PER_CU * bad, "badCUs": bad,
+                      "firstBadCU": 0 if bad else None, "firstBadSimd": 0 if bad else None,
+                      "firstBadGroup": "f32" if bad else None, "firstBadLane": 0 if bad else None,
+                      "splitWaves": 0, "suspectCU": None, "suspectSimd": None,
+                      "transDigest": SIM_ALU_TRANS_DIGEST, "ms": SIM_ALU_MS}
         if bad:
             res["passed"] = False
     if fail:

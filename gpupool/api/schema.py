@@ -196,6 +196,11 @@ DEVICE_STATUS = {
                     "description": "CUs on whose four SIMDs the spec.probe.registerCheck march found "
                                    "the whole vector register file clean (present only when the "
                                    "pool asks for the check)."},
+                "aluVerifiedCUs": {
+                    **_I32,
+                    "description": "CUs on whose four SIMDs the spec.probe.aluCheck instruction program "
+                                   "ended with every digest as expected (present only when the pool "
+                                   "asks for the check)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -454,6 +459,19 @@ MI355X_SPEC = {
                                                  "status.devices[].probe.regsVerifiedCUs. "
                                                  "Adds ~0.06 ms to the 0.77 ms claim-time "
                                                  "probe."},
+                "aluCheck": {**_B, "default": False,
+                             "description": "Also run a fixed program of vector-ALU instructions "
+                                            "(integer, f32, f64, packed f16, cross-lane, "
+                                            "transcendental) on every SIMD of every CU at claim time "
+                                            "and on rechecks: every lane's result digests are compared "
+                                            "bit for bit with a host-computed expectation, the "
+                                            "transcendental ones with the device-wide consensus. A wave "
+                                            "off the expectation fails DeviceProbePassed "
+                                            "(ALUResultMismatch, naming the group, CU, SIMD and lane), "
+                                            "waves that disagree on the transcendental digest fail it as "
+                                            "ALUConsensusSplit, a SIMD no wave covered as "
+                                            "ALUCoverageShort; the clean CUs are reported as "
+                                            "status.devices[].probe.aluVerifiedCUs."},
                 "xgmiPeerCheck": {**_B, "default": True,
                                   "description": "For pools of 2+ GPUs: each GPU copies a "
                                                  "pattern to the next one over xGMI "

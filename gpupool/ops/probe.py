@@ -75,6 +75,9 @@ def lib() -> ctypes.CDLL:
             if hasattr(l, "mi355x_probe_regs"):  # absent from a library built before it
                 l.mi355x_probe_regs.restype = ctypes.c_void_p
                 l.mi355x_probe_regs.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
+            if hasattr(l, "mi355x_probe_alu"):  # absent from a library built before it
+                l.mi355x_probe_alu.restype = ctypes.c_void_p
+                l.mi355x_probe_alu.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
             if hasattr(l, "mi355x_probe_abft_check"):  # absent from a library built before them
                 vp, ull = ctypes.c_void_p, ctypes.c_ulonglong
                 l.mi355x_probe_abft_check.restype = ctypes.c_int
@@ -121,7 +124,7 @@ def identify(dev: int) -> dict:
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
         host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False,
-        **test_hooks: int) -> dict:
+        alu_check: bool = False, **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
     older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
     ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
@@ -136,6 +139,11 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     of every CU marched in both polarities by a workgroup that owns the CU), reported under "regs";
     its knobs and hooks (regsPatterns, regsSalt, regsBlocksPerCU, regsFirst, injectRegFlip=[u, lane,
     bit], injectRegFaultSimd, injectRegFaultXcc, injectRegSkip) go with the test hooks too.
+    ``alu_check`` adds the vector-ALU phase (a fixed program of integer, f32, f64, packed-f16, cross-lane
+    and transcendental instructions on every SIMD of every CU, each lane's digests compared with the
+    host's, the transcendental ones with the device's consensus), reported under "alu"; its knobs and
+    hooks (aluIters, aluBlocksPerCU, aluFirst, aluSeed, injectAluFlip=[group, step, lane, bit],
+    injectAluFaultSimd, injectAluFaultXcc) go with the test hooks too.
     ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults;
@@ -143,7 +151,8 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     element of C instead of row gemm_n/3, column gemm_n/5 — outside C: no fault."""
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, _hook(v)) for k, v in test_hooks.items())),
-                     tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check), bool(reg_check))
+                     tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check), bool(reg_check),
+                     *((True,) if alu_check else ()))
     return _take(lib().mi355x_probe_run(dev, opts))
 
 
@@ -155,7 +164,8 @@ def _hook(v):
 @functools.lru_cache(maxsize=64)
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
               gemm_tile: int, hooks: tuple, low_precision: tuple = (),
-              host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False) -> bytes:
+              host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False,
+              alu_check: bool = False) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
     opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
@@ -168,6 +178,8 @@ def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps:
         opts["ldsCheck"] = 1
     if reg_check:
         opts["regCheck"] = 1
+    if alu_check:
+        opts["aluCheck"] = 1
     return json.dumps(opts).encode()
 
 
@@ -256,6 +268,32 @@ def regs(dev: int, patterns: int = 2, want_stage: int = 0, **hooks) -> dict:
     if buf is not None and "dumpCU" in res:
         res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(regfile.WAVES, regfile.REGISTERS,
                                                                    regfile.LANES).copy()
+    return res
+
+
+def alu(dev: int, iters: int | None = None, want_stage: int = 0, **hooks) -> dict:
+    """The vector-ALU phase alone (``mi355x_probe_alu``): the instruction program of
+    native/src/probe/alu.h on every SIMD of every CU, ``iters`` steps per group (default: the
+    library's). -> the "alu" block of ``run`` plus "device" and "passed". ``want_stage`` 1 | 2:
+    workgroup 0's digests after step 0 / after the last step come back under "data" (uint32
+    [4][6][64]: wave, group, lane; ``gpupool.ops.alu`` is the exact twin of the first five groups),
+    "dumpCU" names the CU it ran on and "dumpSimds" the SIMD of each of its waves. ``hooks``:
+    aluBlocksPerCU, aluSeed, requireAllCUs, injectAluFlip=[group, step, lane, bit],
+    injectAluFaultSimd, injectAluFaultXcc."""
+    import numpy as np
+
+    from . import alu as twin
+    if not hasattr(lib(), "mi355x_probe_alu"):
+        raise RuntimeError("libmi355x_probe.so predates the vector-ALU check: rebuild it")
+    opts = {**({"aluIters": int(iters)} if iters is not None else {}), **{k: _hook(v) for k, v in hooks.items()}}
+    buf, n = None, 0
+    if want_stage:
+        opts["aluDumpStage"] = int(want_stage)
+        n = twin.DUMP_BYTES
+        buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_alu(dev, json.dumps(opts).encode(), buf, n))
+    if buf is not None and "dumpCU" in res:
+        res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(twin.WAVES, len(twin.GROUPS), twin.LANES).copy()
     return res
 
 

@@ -117,6 +117,40 @@ char* mi355x_probe_run(int device, const char* opts_json);
  * min(image_bytes, 524288) bytes land in image, and the report names "dumpCU", the CU key that workgroup ran
  * on, and "dumpSimds", the SIMD of each of its four waves. A bad device: {"passed":false,"error":...}. */
 char* mi355x_probe_regs(int device, const char* opts_json, void* image, size_t image_bytes);
+/* Vector ALUs (opt-in): "aluCheck":1 in mi355x_probe_run's options runs a fixed program of vector-ALU
+ * instructions on every SIMD of every CU: one kernel of 256-thread workgroups with ordinary register counts,
+ * "aluBlocksPerCU" of them per CU (1..64). Six groups (0 int, 1 f32, 2 f64, 3 f16, 4 lane, 5 trans) of
+ * "aluIters" steps (1..4096) over a 32-bit digest per lane and group; every operand of a step is
+ * pattern_word(group << 32 | step << 12 | operand << 6 | lane, seed) ^ digest, every result is folded into the
+ * digest, (rotl(h, 5) ^ r) * 0x9E3779B1. The seed is 0x414C5500 + device ("aluSeed" overrides it) and is not
+ * salted per run: the library computes the expected digests of the five exact groups on the host
+ * (native/src/probe/alu_ref.h) once per context and (seed, iters) and every lane compares its own with
+ * them. The transcendental group is compared with the device-wide consensus: the first wave publishes its
+ * 64-bit digest, every other wave compares. The phase rides the MFMA stream behind the MFMA and
+ * low-precision phases ("aluFirst":1 ahead of them), behind the LDS and register-file phases where asked
+ * for, with "overlap":0 last on the one stream. The report then gains, after "regs",
+ *   "alu":{"ok","iters","workgroups","waves","wavesPerSimd","simdsTested","simdsVerified","cusVerified","perXcd",
+ *          "badWaves","badLanes","badCUs","firstBadCU","firstBadSimd","firstBadGroup","firstBadLane","splitWaves",
+ *          "suspectCU","suspectSimd","transDigest","ms"}
+ * wavesPerSimd: the waves that ran on SIMD 0..3 of their CU (HW_ID[5:4]), waves their sum; a wave whose every
+ * check passed marks its (CU, SIMD) verified, one that failed marks it bad: simdsTested = either,
+ * simdsVerified = verified and not bad, perXcd those per XCD, cusVerified the CUs with all four. badWaves /
+ * badLanes count mismatches against the host, badCUs the CUs with a SIMD marked bad; firstBadCU (the 11-bit CU key), firstBadSimd, firstBadGroup (a
+ * name) and firstBadLane name the lowest, or are null. splitWaves counts the waves whose transcendental
+ * digest differs from the published one, transDigest (16 hex digits); suspectCU / suspectSimd name the
+ * publisher when more than half of the waves differ and the first differing wave otherwise (null without a
+ * split). ok = badWaves 0, splitWaves 0 and, unless "requireAllCUs":0, simdsVerified = 4 x CUs; "passed" also
+ * needs it. Without the option: no "alu" key, no launch, allocation or event. Test hooks (either, or the dump
+ * below, selects the kernel's test instantiation): "injectAluFlip":[group, step, lane, bit] XORs that bit into
+ * the last result of that step of that group in that lane of every wave, "injectAluFaultSimd":s /
+ * "injectAluFaultXcc":x only on SIMD s / on XCD x; a value out of range switches the hook off.
+ *
+ * mi355x_probe_alu: the phase alone, on the device's first stream, under the device's probe lock; the "alu"
+ * block (after "device" and "passed") is the whole report. opts as above (without "aluCheck"). With dump and
+ * "aluDumpStage":1|2, workgroup 0's digests uint32[4][6][64] (wave, group, lane) after step 0 / after the
+ * last step land in dump (the first min(dump_bytes, 6144) bytes), and the report names "dumpCU" and
+ * "dumpSimds" as mi355x_probe_regs does. A bad device: {"passed":false,"error":...}. */
+char* mi355x_probe_alu(int device, const char* opts_json, void* dump, size_t dump_bytes);
 /* The LDS phase alone, on the device's first stream, under the device's probe lock; the "lds" block (after
  * "device" and "passed") is the whole report. opts as above (without "ldsCheck"). With image and
  * "ldsDumpStage":1|2|3, workgroup 0's LDS is copied out — 1 after the first write, 2 after the first

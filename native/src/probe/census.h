@@ -21,6 +21,13 @@ __device__ __forceinline__ int cu_key() {
   return static_cast<int>(((xcc & 7u) << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u));
 }
 
+// HW_ID.SIMD_ID, bits [5:4] in the same layout: which of the CU's four SIMDs the wave runs on.
+__device__ __forceinline__ uint32_t simd_id() {
+  unsigned hw;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  return (hw >> 4) & 3u;
+}
+
 __device__ __forceinline__ void mark_cu(unsigned long long* map) {
   const int k = cu_key();
   atomicOr(&map[k >> 6], 1ull << (k & 63));

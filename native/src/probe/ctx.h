@@ -64,6 +64,18 @@ struct DeviceCtx {
   uint32_t regs_runs = 0;     // the default "regsSalt"
   void* regs_dump = nullptr;  // device image uint32[4][512][64] (mi355x_probe_regs with an image)
   int regs_attr[2][2] = {};
+  // vector-ALU phase ("aluCheck"): events, counter sets and pinned result as the LDS phase's.
+  // alu_exp holds the host's expectation uint32[5][64] of (alu_exp_seed, alu_exp_iters), computed
+  // and uploaded once per context and pair; alu_exp1 the one of the dump's stage 1 (one step).
+  hipEvent_t alu_ev[2] = {};
+  unsigned long long* alu_cnt = nullptr;  // device, 2 sets
+  unsigned long long* alu_res = nullptr;  // pinned copy of the set a run used
+  int alu_set = 0;
+  bool alu_clean = false;
+  uint32_t* alu_exp = nullptr;  // device
+  uint32_t alu_exp_seed = 0;
+  int alu_exp_iters = 0;        // 0: nothing uploaded yet
+  void* alu_dump = nullptr;     // device uint32[4][6][64] (mi355x_probe_alu with a dump buffer)
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;

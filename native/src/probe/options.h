@@ -316,6 +316,86 @@ struct Plan {
 
 }  // namespace regs
 
+namespace alu {
+
+constexpr int kPlanGroups = 6;  // int, f32, f64, f16, lane, trans (alu_ref.h kGroups)
+constexpr int kPlanLanes = 64;
+constexpr int kSimdsPerCU = 4;
+// workgroup 0's digests as mi355x_probe_alu copies them out: uint32 [wave][group][lane]
+constexpr size_t kDumpBytes = static_cast<size_t>(kSimdsPerCU) * kPlanGroups * kPlanLanes * 4;
+// Steps per group ("aluIters" selects per run): the largest power of two at which the phase adds no
+// more to the claim probe's p50 (1 GiB, 2048^3, overlapped) than the register check's recorded +0.060 ms.
+// Measured on the MI355X at 1 workgroup per CU, each step count alternating with the plain probe for
+// 40 rounds (scripts/alu_claim_probe_cost.py, profiles/alu_claim_probe_cost.json and _run1.json), added
+// p50 in two runs: 1..32 steps +0.025..0.036 ms (the launch, the atomics and the expectation load, not
+// the steps), 64 +0.032 / +0.039, 128 +0.061 / +0.055, 256 +0.136, 512 +0.30, 1024 +0.82. 128 sits on
+// the limit and crossed it in one of the two runs, so the default is 64. The kernel alone takes
+// 0.027 ms at 1 step and 1.33 us per step above ~16 (0.105 ms at 64, 1.39 ms at 1024).
+constexpr int kIters = 64;
+constexpr int kMaxIters = 4096;  // the step has 20 bits in an operand's index; the twin is exact rational
+// Workgroups per CU of the grid ("aluBlocksPerCU" selects per run). The kernel makes no exclusivity
+// claim (28 VGPRs, no LDS), so coverage is per (CU, SIMD) and rests on the dispatcher. Same
+// measurement, 400 runs per factor and setting, the factors interleaved: 1, 2, 4, 8 and 16 all verified
+// 4 x 256 SIMDs in every run, alone on the GPU and inside the overlapped claim probe at either
+// position. Unlike the LDS and
+// register kernels this one needs nothing of a CU to itself, so its workgroups land beside the HBM
+// test's waves. The default is the smallest factor, 1: kernel p50 alone 0.106 ms at 64 steps against
+// 0.165 / 0.293 / 0.552 / 1.07 at 2 / 4 / 8 / 16 (waves of one SIMD run one after the other), claim
+// probe 0.80 ms against 0.87 / 0.99 / 1.25 / 1.76 behind the MFMA phase. Coverage stays part of ok.
+constexpr int kBlocksPerCU = 1;
+constexpr int kMaxBlocksPerCU = 64;
+// Where the phase sits on the MFMA stream ("aluFirst" selects per run): 0 behind the MFMA and
+// low-precision phases, 1 ahead of them. Same measurement, 40 alternating rounds at 1 workgroup per CU
+// and 64 steps: the claim probe grows 0.765 -> 0.800 ms behind the MFMA phase (+0.034) and -> 0.804
+// ahead of it (+0.038); at 32 steps the run before had it the other way round (+0.031 behind, +0.028
+// ahead). The two places differ by less than the plain probe's odd/even-round spread
+// (0.007 ms): the default is the one that added less at the default step count, behind.
+constexpr int kFirst = 0;
+constexpr uint32_t kPlanSeedBase = 0x414C5500u;  // alu_ref.h kSeedBase
+
+// What one run of the phase does (options of mi355x_probe_run with "aluCheck" and of mi355x_probe_alu).
+struct Plan {
+  bool on = false;  // false: the phase is off
+  int iters = kIters;
+  int blocks_per_cu = kBlocksPerCU;
+  // "aluSeed", else kPlanSeedBase + dev: fixed per device and never salted per run, because the
+  // host's expectation table is computed once per (seed, iters) and cached in the context
+  uint32_t seed = 0;
+  // test hooks, each off (-1) when out of range
+  int flip_group = -1, flip_step = -1, flip_lane = -1, flip_bit = -1;  // "injectAluFlip":[group, step, lane, bit]
+  int fault_simd = -1;                                                 // "injectAluFaultSimd": the flip only on that SIMD
+  int fault_xcc = -1;                                                  // "injectAluFaultXcc": the flip only on that XCD
+  int dump_stage = 0;                                                  // "aluDumpStage" 1 | 2, only with a caller buffer
+  // the test instantiation of the kernel runs only when a hook or the dump asks for it
+  bool test_kernel() const { return flip_group >= 0 || dump_stage != 0; }
+  static Plan parse(const char* json, int dev) {
+    Plan pl;
+    pl.on = true;
+    pl.iters = static_cast<int>(std::min<long long>(kMaxIters, std::max(1LL, opt_int(json, "aluIters", kIters))));
+    pl.blocks_per_cu =
+        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "aluBlocksPerCU", kBlocksPerCU))));
+    const long long seed = opt_int(json, "aluSeed", -1);
+    pl.seed = seed >= 0 ? static_cast<uint32_t>(seed) : kPlanSeedBase + static_cast<uint32_t>(dev);
+    long long f[4];
+    if (opt_ints(json, "injectAluFlip", f, 4) && f[0] >= 0 && f[0] < kPlanGroups && f[1] >= 0 && f[1] < pl.iters &&
+        f[2] >= 0 && f[2] < kPlanLanes && f[3] >= 0 && f[3] < 32) {
+      pl.flip_group = static_cast<int>(f[0]);
+      pl.flip_step = static_cast<int>(f[1]);
+      pl.flip_lane = static_cast<int>(f[2]);
+      pl.flip_bit = static_cast<int>(f[3]);
+    }
+    const long long simd = opt_int(json, "injectAluFaultSimd", -1);
+    pl.fault_simd = simd >= 0 && simd < kSimdsPerCU ? static_cast<int>(simd) : -1;
+    const long long xcc = opt_int(json, "injectAluFaultXcc", -1);
+    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
+    const long long stage = opt_int(json, "aluDumpStage", 0);
+    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    return pl;
+  }
+};
+
+}  // namespace alu
+
 // Where the GEMM fault hooks corrupt C (test hooks "injectGemmFaultRow" / "injectGemmFaultCol"):
 // -1 is the element the hooks always took, row n/3 and column n/5; any other value outside [0, n)
 // means no fault, like "injectFlipAtChunk".
@@ -373,6 +453,8 @@ struct ProbeOptions {
   bool lds_first = lds::kFirst == 1;  // "ldsFirst": 1 ahead of the MFMA phase on its stream, 0 behind it (A/B)
   regs::Plan regs;                 // "regCheck"; !on: off, and none of its options is looked up
   bool regs_first = regs::kFirst == 1;  // "regsFirst": as "ldsFirst"
+  alu::Plan alu;                   // "aluCheck"; !on: off, and none of its options is looked up
+  bool alu_first = alu::kFirst == 1;  // "aluFirst": as "ldsFirst"
 
   static ProbeOptions parse(const char* json, int dev = 0) {
     ProbeOptions o;
@@ -419,6 +501,11 @@ struct ProbeOptions {
       o.regs = regs::Plan::parse(json, dev);
       o.regs.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_regs
       o.regs_first = opt_int(json, "regsFirst", regs::kFirst) == 1;
+    }
+    if (opt_bool(json, "aluCheck", false)) {
+      o.alu = alu::Plan::parse(json, dev);
+      o.alu.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_alu
+      o.alu_first = opt_int(json, "aluFirst", alu::kFirst) == 1;
     }
     return o;
   }

@@ -46,7 +46,7 @@
 #include <cstdint>
 
 #include "arena.h"    // kCuMapWords
-#include "census.h"   // cu_key, count_cus
+#include "census.h"   // cu_key, simd_id, count_cus
 #include "ctx.h"      // DeviceCtx: the phase's events, counters and pinned result
 #include "hbm.h"      // pattern16, umin64
 #include "options.h"  // regs::Plan
@@ -80,13 +80,6 @@ struct KernelArgs {
   unsigned long long* cnt;   // this run's counter set
   unsigned long long* next;  // the next run's, reset here
 };
-
-// HW_ID.SIMD_ID, bits [5:4] in the GFX9 layout cu_key() decodes.
-__device__ __forceinline__ uint32_t simd_id() {
-  unsigned hw;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  return (hw >> 4) & 3u;
-}
 
 // ------------------------------------------------------------------ the asm text
 // Assembler repetition: the symbol rf_i walks the register indices of a range, up or down.

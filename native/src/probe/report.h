@@ -221,6 +221,65 @@ inline std::string regs_block(const RegsResult& r) {
   return out + "}";
 }
 
+// The vector-ALU phase: which (CU, SIMD) pairs a wave ran the whole instruction program on with every
+// digest as expected. first_bad is (CU key << 32) | SIMD << 16 | group << 8 | lane of the lowest
+// mismatch against the host's expectation, all-ones = none. The transcendental group is checked by
+// consensus: trans_digest is the value the first wave published, split_waves the waves that got
+// another one, suspect (CU key << 2 | SIMD, or -1) the publisher when more than half of the waves
+// differ from it and the first differing wave otherwise.
+struct AluResult {
+  int iters = 0;
+  unsigned long long workgroups = 0;
+  unsigned long long waves_per_simd[4] = {};
+  int expected = 0;  // CUs of the device
+  int simds_tested = 0, simds_verified = 0, cus_verified = 0;
+  int per_xcd[8] = {};  // verified SIMDs
+  unsigned long long bad_waves = 0, bad_lanes = 0, first_bad = ~0ull;
+  int bad_cus = 0;  // CUs with a SIMD in the bad map (a mismatch or a split)
+  unsigned long long split_waves = 0;
+  long long suspect = -1;
+  unsigned long long trans_digest = 0;
+  float ms = 0;
+  bool require_all = true;  // "requireAllCUs"
+  int dump_cu = -1;         // mi355x_probe_alu with a dump buffer: the CU key of the dumped workgroup
+  int dump_simds[4] = {};   // ... and the SIMD each of its four waves ran on
+  unsigned long long waves() const { return waves_per_simd[0] + waves_per_simd[1] + waves_per_simd[2] + waves_per_simd[3]; }
+  bool ok() const {
+    return bad_waves == 0 && split_waves == 0 && (!require_all || simds_verified >= 4 * expected);
+  }
+};
+
+inline std::string alu_block(const AluResult& r) {
+  static const char* const kNames[] = {"int", "f32", "f64", "f16", "lane", "trans"};
+  std::string per = "[", per_simd = "[";
+  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
+  for (int s = 0; s < 4; ++s) per_simd += (s ? "," : "") + std::to_string(r.waves_per_simd[s]);
+  const bool none = r.first_bad == ~0ull;
+  auto field = [&](int shift, unsigned long long mask) {
+    return none ? std::string("null") : std::to_string((r.first_bad >> shift) & mask);
+  };
+  const unsigned long long g = (r.first_bad >> 8) & 0xFF;
+  char hex[24];
+  std::snprintf(hex, sizeof hex, "\"%016llx\"", r.trans_digest);
+  std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"iters\":" + std::to_string(r.iters) +
+                    ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"waves\":" + std::to_string(r.waves()) +
+                    ",\"wavesPerSimd\":" + per_simd + "]" + ",\"simdsTested\":" + std::to_string(r.simds_tested) +
+                    ",\"simdsVerified\":" + std::to_string(r.simds_verified) +
+                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"badWaves\":" + std::to_string(r.bad_waves) + ",\"badLanes\":" + std::to_string(r.bad_lanes) +
+                    ",\"badCUs\":" + std::to_string(r.bad_cus) +
+                    ",\"firstBadCU\":" + field(32, 0xFFFFFFFFull) + ",\"firstBadSimd\":" + field(16, 3) +
+                    ",\"firstBadGroup\":" + (none || g > 5 ? std::string("null") : "\"" + std::string(kNames[g]) + "\"") +
+                    ",\"firstBadLane\":" + field(0, 63) + ",\"splitWaves\":" + std::to_string(r.split_waves) +
+                    ",\"suspectCU\":" + (r.suspect < 0 ? std::string("null") : std::to_string(r.suspect >> 2)) +
+                    ",\"suspectSimd\":" + (r.suspect < 0 ? std::string("null") : std::to_string(r.suspect & 3)) +
+                    ",\"transDigest\":" + hex + ",\"ms\":" + jnum(r.ms);
+  if (r.dump_cu >= 0)
+    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
+           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  return out + "}";
+}
+
 // Host wall-clock of a probe's steps.
 struct PhaseTimes {
   bool arena_reused = false;
@@ -240,7 +299,7 @@ inline std::string phases_block(const PhaseTimes& t) {
 inline std::string device_head(int dev) { return "\"device\":" + std::to_string(dev); }
 
 // Everything mi355x_probe_run reports. "cus" only with the MFMA phase, "lowp" only with a dtype,
-// "hostLink", "lds" and "regs" only when asked for.
+// "hostLink", "lds", "regs" and "alu" only when asked for.
 struct ProbeReport {
   int dev = 0;
   std::string uuid, arch;
@@ -254,11 +313,13 @@ struct ProbeReport {
   LdsResult lds;
   bool has_regs = false;
   RegsResult regs;
+  bool has_alu = false;
+  AluResult alu;
   double total_ms = 0;
   PhaseTimes phases;
   bool passed() const {
     bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok()) && (!has_lds || lds.ok()) &&
-              (!has_regs || regs.ok());
+              (!has_regs || regs.ok()) && (!has_alu || alu.ok());
     for (const LowpResult& l : lowp) ok = ok && l.ok;
     return ok;
   }
@@ -280,6 +341,7 @@ inline std::string probe_report_open(const ProbeReport& r) {
   if (r.has_host_link) out += ",\"hostLink\":" + host_link_block(r.host_link);
   if (r.has_lds) out += ",\"lds\":" + lds_block(r.lds);
   if (r.has_regs) out += ",\"regs\":" + regs_block(r.regs);
+  if (r.has_alu) out += ",\"alu\":" + alu_block(r.alu);
   out += ",\"ms\":" + jnum(r.total_ms);
   out += ",\"phases\":" + phases_block(r.phases);
   return out;

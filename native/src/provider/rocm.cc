@@ -99,6 +99,8 @@ Json DeviceView::status_json() const {
       p["ldsVerifiedCUs"] = probe.path("lds.cusVerified");
     if (probe["regs"].is_object())  // spec.probe.registerCheck: the CUs whose register files tested clean
       p["regsVerifiedCUs"] = probe.path("regs.cusVerified");
+    if (probe["alu"].is_object())  // spec.probe.aluCheck: the CUs whose four SIMDs' vector ALUs tested clean
+      p["aluVerifiedCUs"] = probe.path("alu.cusVerified");
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)

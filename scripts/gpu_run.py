@@ -109,6 +109,11 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # phase's cost in the claim probe (give regs_claim_probe_cost.py --parent-lib DIR
         # --parent-lib-copy DIR2 by hand for the default-path A/B and its null pair)
         "regs": [("regs_claim_probe_cost", [PY, "scripts/regs_claim_probe_cost.py"], 600, {})],
+        # spec.probe.aluCheck: the grid factor that covers every SIMD, the cheaper position, the step count
+        # that fits the register check's +0.060 ms and the phase's cost in the claim probe (give
+        # alu_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
+        # A/B and its null pair)
+        "alu": [("alu_claim_probe_cost", [PY, "scripts/alu_claim_probe_cost.py"], 600, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],
