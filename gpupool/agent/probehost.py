@@ -155,6 +155,7 @@ class _HipKernel:
                           **({"lds_check": True} if a.get("ldsCheck") else {}),
                           **({"reg_check": True} if a.get("registerCheck") else {}),
                           **({"alu_check": True} if a.get("aluCheck") else {}),
+                          **({"atom_check": True} if a.get("atomicsCheck") else {}),
                           **{k: int(v) for k, v in (a.get("testHooks") or {}).items()})
         if op == "sweep":
             return hp.hbm_sweep(self.ordinal(a.get("hipUUID")), int(a["offset"]), int(a["bytes"]),

@@ -242,6 +242,7 @@ class Prober:
         lds = bool(opts.get("ldsCheck"))  # spec.probe.ldsCheck: the per-CU LDS phase
         regs = bool(opts.get("registerCheck"))  # spec.probe.registerCheck: the register-file phase
         alu = bool(opts.get("aluCheck"))  # spec.probe.aluCheck: the vector-ALU phase
+        atomics = bool(opts.get("atomicsCheck"))  # spec.probe.atomicsCheck: the atomic-unit phase
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -265,6 +266,8 @@ class Prober:
                 args["registerCheck"] = True
             if alu:
                 args["aluCheck"] = True
+            if atomics:
+                args["atomicsCheck"] = True
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -280,14 +283,15 @@ class Prober:
                                     overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
                                     host_link_bytes=hostlink, **({"lds_check": True} if lds else {}),
                                     **({"reg_check": True} if regs else {}),
-                                    **({"alu_check": True} if alu else {}))
+                                    **({"alu_check": True} if alu else {}),
+                                    **({"atom_check": True} if atomics else {}))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
                     (["--low-precision", ",".join(lowp)] if lowp else []) + \
                     (["--host-link-bytes", str(hostlink)] if hostlink else []) + \
                     (["--lds-check"] if lds else []) + (["--register-check"] if regs else []) + \
-                    (["--alu-check"] if alu else [])
+                    (["--alu-check"] if alu else []) + (["--atomics-check"] if atomics else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -340,7 +344,8 @@ class Prober:
         spec.probe.registerCheck the bits flipped in a SIMD's vector register file, the CUs not
         covered, or a kernel that did not own the file it tested; for spec.probe.aluCheck the waves
         whose vector-ALU digests differ from the host's, the waves that disagree on the
-        transcendental digest, or the SIMDs not covered)."""
+        transcendental digest, or the SIMDs not covered; for spec.probe.atomicsCheck the slots an
+        atomic left off the host's value, the returned values off it, or the CUs not covered)."""
         if res.get("passed") or res.get("error"):
             return res
         why = []
@@ -423,6 +428,23 @@ class Prober:
             if not (alu.get("badWaves") or alu.get("splitWaves")) or \
                     (expected and alu.get("simdsTested", 0) < 4 * expected):
                 why.append(f"ALUCoverageShort: {alu.get('simdsVerified')}/{4 * expected if expected else '?'} SIMDs")
+        atom = res.get("atomics") or {}
+        if atom and not atom.get("ok", True):
+            counts = [atom.get(k) or 0 for k in ("ldsBadSlots", "l2BadSlots", "devBadSlots", "badReturns", "ticketFaults")]
+            if any(counts):
+                where = ""
+                if atom.get("firstBadLayer") == "dev":
+                    x = atom.get("firstBadXcc")
+                    where = f"first in the {'all-XCD' if x == 8 else f'XCD {x}'} row slot {atom.get('firstBadSlot')}"
+                else:
+                    k = int(atom.get("firstBadCU") or 0)  # the 11-bit key: xcc[10:8] se[7:5] sh[4] cu[3:0]
+                    where = f"first on CU {k >> 8}/{(k >> 5) & 7}/{(k >> 4) & 1}/{k & 15} slot {atom.get('firstBadSlot')}"
+                why.append(f"AtomicResultMismatch({atom.get('firstBadLayer')}/{atom.get('firstBadOp')}): "
+                           f"{sum(counts)} slot(s) on {atom.get('badCUs')} CU(s), {where}")
+            expected = cus.get("expected")
+            if not any(counts) or (expected and atom.get("cusTested", 0) < expected):
+                why.append(f"AtomicCoverageShort: {atom.get('cusVerified')}/{expected or '?'} CUs verified, "
+                           f"per XCD {atom.get('perXcd')}")
         res["error"] = "; ".join(why) or "probe failed"
         return res
 

@@ -34,6 +34,14 @@ SIM_ALU_BLOCKS_PER_CU = 1
 SIM_ALU_ITERS = 64
 SIM_ALU_MS = 0.14
 SIM_ALU_TRANS_DIGEST = "0" * 16
+# the atomic-unit phase's grid factor, step count, layer mask and kernel time (native/src/probe/options.h
+# atom::kBlocksPerCU, atom::kIters, atom::kLayerMask; profiles/atomics_claim_probe_cost.json and _run2.json:
+# every CU verified at factor 1 in 400 runs per setting, 2 steps add +0.037 ms to the claim probe in both
+# runs, the two kernels take 0.10 ms alone)
+SIM_ATOM_BLOCKS_PER_CU = 1
+SIM_ATOM_ITERS = 2
+SIM_ATOM_LAYERS = 7
+SIM_ATOM_MS = 0.1
 SIM_LOWP_TFLOPS = {"fp8": 696.0, "mxfp8": 477.0, "mxfp4": 523.0}
 
 
@@ -143,6 +151,30 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
                       "firstBadGroup": "f32" if bad else None, "firstBadLane": 0 if bad else None,
                       "splitWaves": 0, "suspectCU": None, "suspectSimd": None,
                       "transDigest": SIM_ALU_TRANS_DIGEST, "ms": SIM_ALU_MS}
+        if bad:
+            res["passed"] = False
+    # spec.probe.atomicsCheck: the block the gfx950 probe reports; the overlay's ``atomicsFault: n`` marks
+    # n CUs bad, the workgroup on each with one slot of the LDS table off the host's value, the first
+    # on the CU with key 0, op add, slot 0
+    if opts.get("atomicsCheck"):
+        cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
+        bad = min(cus, int(fault(dev, "atomicsFault") or 0))
+        full = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
+        per = list(full)
+        left = bad
+        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
+            take = min(left, per[x])
+            per[x] -= take
+            left -= take
+        wg = SIM_ATOM_BLOCKS_PER_CU * cus
+        res["atomics"] = {"ok": bad == 0, "iters": SIM_ATOM_ITERS, "layers": SIM_ATOM_LAYERS, "workgroups": wg,
+                          "wgPerXcd": [SIM_ATOM_BLOCKS_PER_CU * n for n in full], "cusTested": cus,
+                          "cusVerified": cus - bad, "perXcd": per, "badCUs": bad,
+                          "badWorkgroups": SIM_ATOM_BLOCKS_PER_CU * bad, "ldsBadSlots": SIM_ATOM_BLOCKS_PER_CU * bad,
+                          "l2BadSlots": 0, "devBadSlots": 0, "badReturns": 0, "ticketFaults": 0,
+                          "firstBadCU": 0 if bad else None, "firstBadLayer": "lds" if bad else None,
+                          "firstBadOp": "add" if bad else None, "firstBadSlot": 0 if bad else None,
+                          "firstBadXcc": 0 if bad else None, "ms": SIM_ATOM_MS}
         if bad:
             res["passed"] = False
     if fail:

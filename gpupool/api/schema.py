@@ -201,6 +201,11 @@ DEVICE_STATUS = {
                     "description": "CUs on whose four SIMDs the spec.probe.aluCheck instruction program "
                                    "ended with every digest as expected (present only when the pool "
                                    "asks for the check)."},
+                "atomicsVerifiedCUs": {
+                    **_I32,
+                    "description": "CUs on which every workgroup of the spec.probe.atomicsCheck program "
+                                   "ended with every atomic's final and returned value as expected "
+                                   "(present only when the pool asks for the check)."},
                 "ms": {"type": "number"},
                 "backend": _S,
                 "message": _S,
@@ -472,6 +477,19 @@ MI355X_SPEC = {
                                             "ALUConsensusSplit, a SIMD no wave covered as "
                                             "ALUCoverageShort; the clean CUs are reported as "
                                             "status.devices[].probe.aluVerifiedCUs."},
+                "atomicsCheck": {**_B, "default": False,
+                                 "description": "Also run a fixed program of atomic read-modify-write "
+                                                "instructions (integer, 64-bit, f32, f64, packed f16 / bf16, "
+                                                "exchange, compare-and-swap) on every CU at claim time and on "
+                                                "rechecks: through the CU's LDS atomic unit, through the L2 "
+                                                "atomic units on memory private to a workgroup, and at device "
+                                                "scope on rows that every XCD's workgroups add to. Every final "
+                                                "value and every returned value is compared with a "
+                                                "host-computed expectation. A value off it fails "
+                                                "DeviceProbePassed (AtomicResultMismatch, naming layer, op, CU "
+                                                "or row and slot), a CU no workgroup reached fails it as "
+                                                "AtomicCoverageShort; the clean CUs are reported as "
+                                                "status.devices[].probe.atomicsVerifiedCUs."},
                 "xgmiPeerCheck": {**_B, "default": True,
                                   "description": "For pools of 2+ GPUs: each GPU copies a "
                                                  "pattern to the next one over xGMI "

@@ -133,7 +133,7 @@ def cmd_describe(c: Client, ns: str, args) -> int:
         print("  " + yaml.safe_dump(st, sort_keys=False).rstrip().replace("\n", "\n  "))
     if devs:
         print("Devices:")
-        print(f"  {'INDEX':<6}{'UUID':<42}{'HEALTH':<11}{'ADV':<5}{'PROBE':<88}PODS")
+        print(f"  {'INDEX':<6}{'UUID':<42}{'HEALTH':<11}{'ADV':<5}{'PROBE':<100}PODS")
         for d in devs:
             p = d.get("probe") or {}
             probe = (f"{'ok' if p.get('passed') else 'FAIL'} {p.get('hbmGBps', 0):.0f}GB/s "
@@ -148,9 +148,11 @@ def cmd_describe(c: Client, ns: str, args) -> int:
                 probe += f" regs {p['regsVerifiedCUs']}CU"
             if p.get("aluVerifiedCUs") is not None:  # spec.probe.aluCheck: CUs whose four SIMDs' vector ALUs tested clean
                 probe += f" alu {p['aluVerifiedCUs']}CU"
+            if p.get("atomicsVerifiedCUs") is not None:  # spec.probe.atomicsCheck: CUs whose atomic units tested clean
+                probe += f" atomics {p['atomicsVerifiedCUs']}CU"
             print(f"  {d.get('index', ''):<6}{d.get('hipUUID') or d['uuid']:<42}"
                   f"{d.get('health', ''):<11}{'yes' if d.get('advertised') else 'no':<5}"
-                  f"{probe:<88}{','.join(d.get('pods', [])) or '-'}")
+                  f"{probe:<100}{','.join(d.get('pods', [])) or '-'}")
             for r in d.get("reasons") or []:
                 print(f"        ! {r}")
     if conds:

@@ -78,6 +78,9 @@ def lib() -> ctypes.CDLL:
             if hasattr(l, "mi355x_probe_alu"):  # absent from a library built before it
                 l.mi355x_probe_alu.restype = ctypes.c_void_p
                 l.mi355x_probe_alu.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
+            if hasattr(l, "mi355x_probe_atomics"):  # absent from a library built before it
+                l.mi355x_probe_atomics.restype = ctypes.c_void_p
+                l.mi355x_probe_atomics.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t]
             if hasattr(l, "mi355x_probe_abft_check"):  # absent from a library built before them
                 vp, ull = ctypes.c_void_p, ctypes.c_ulonglong
                 l.mi355x_probe_abft_check.restype = ctypes.c_int
@@ -124,7 +127,7 @@ def identify(dev: int) -> dict:
 def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 4096,
         patterns: int = 2, gemm_reps: int = 1, gemm_tile: int = 256, mfma_low_precision=(),
         host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False,
-        alu_check: bool = False, **test_hooks: int) -> dict:
+        alu_check: bool = False, atom_check: bool = False, **test_hooks: int) -> dict:
     """Probe HIP device ``dev``. ``gemm_tile`` 256 (default, the glds 256x256 kernel) or 128 (the
     older register-staged kernel, for A/B). ``mfma_low_precision``: names out of ``lowp.DTYPES``
     ("fp8", "mxfp8", "mxfp4"); each adds a census, a 256^3 GEMM against a VALU reference and the
@@ -144,6 +147,12 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     host's, the transcendental ones with the device's consensus), reported under "alu"; its knobs and
     hooks (aluIters, aluBlocksPerCU, aluFirst, aluSeed, injectAluFlip=[group, step, lane, bit],
     injectAluFaultSimd, injectAluFaultXcc) go with the test hooks too.
+    ``atom_check`` adds the atomic-unit phase (a fixed program of atomic read-modify-write instructions
+    through every CU's LDS atomic unit, through the L2 atomic units and at device scope across the XCDs,
+    every final and returned value compared with the host's), reported under "atomics"; its knobs and
+    hooks (atomIters, atomBlocksPerCU, atomLayers, atomFirst, atomSeed, injectAtomSkip=[layer, op, step,
+    lane], injectAtomFlip=[layer, op, step, lane, bit], injectAtomFaultXcc, injectAtomFaultWorkgroup) go
+    with the test hooks too.
     ``test_hooks``: injectBitFlips=N (N bits spread over
     the HBM region) / injectFlipAtChunk=i (bit 0 of 16-byte chunk i) / injectGemmFault=1 corrupt
     the device buffers between compute and check so tests can prove the checkers catch faults;
@@ -152,7 +161,7 @@ def run(dev: int, hbm_bytes: int = 1 << 30, mfma: bool = True, gemm_n: int = 409
     opts = _run_opts(int(hbm_bytes), bool(mfma), int(gemm_n), int(patterns), int(gemm_reps),
                      int(gemm_tile), tuple(sorted((k, _hook(v)) for k, v in test_hooks.items())),
                      tuple(mfma_low_precision), int(host_link_bytes), bool(lds_check), bool(reg_check),
-                     *((True,) if alu_check else ()))
+                     **{k: True for k, on in (("alu_check", alu_check), ("atom_check", atom_check)) if on})
     return _take(lib().mi355x_probe_run(dev, opts))
 
 
@@ -165,7 +174,7 @@ def _hook(v):
 def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps: int,
               gemm_tile: int, hooks: tuple, low_precision: tuple = (),
               host_link_bytes: int = 0, lds_check: bool = False, reg_check: bool = False,
-              alu_check: bool = False) -> bytes:
+              alu_check: bool = False, atom_check: bool = False) -> bytes:
     # An agent probes with a handful of option sets: encode each once. Encoding it per claim cost
     # 0.05 ms on a CPU woken from idle (profiles/r4n_probe_idle_binding.json).
     opts = {"hbmBytes": hbm_bytes, "mfma": mfma, "gemmN": gemm_n, "patterns": patterns,
@@ -180,6 +189,8 @@ def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps:
         opts["regCheck"] = 1
     if alu_check:
         opts["aluCheck"] = 1
+    if atom_check:
+        opts["atomCheck"] = 1
     return json.dumps(opts).encode()
 
 
@@ -294,6 +305,44 @@ def alu(dev: int, iters: int | None = None, want_stage: int = 0, **hooks) -> dic
     res = _take(lib().mi355x_probe_alu(dev, json.dumps(opts).encode(), buf, n))
     if buf is not None and "dumpCU" in res:
         res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(twin.WAVES, len(twin.GROUPS), twin.LANES).copy()
+    return res
+
+
+def atomics(dev: int, iters: int | None = None, want_stage: int = 0, **hooks) -> dict:
+    """The atomic-unit phase alone (``mi355x_probe_atomics``): the program of
+    native/src/probe/atomics.h on every CU, ``iters`` steps per layer (default: the library's). -> the
+    "atomics" block of ``run`` plus "device" and "passed". ``want_stage`` 1 | 2: workgroup 0's data comes
+    back as uint32 arrays: "ldsTable" [2688], "ldsTable16" [1408] (the second addressing), "ldsDigests"
+    and "l2Digests" [4][64] as they stood after step 0 / after the last step, and, of the whole run either
+    way, "region" [2688] and "devRows" [9][1408] as the verifying kernel read them, and
+    "wgKeys" / "wgXcc", the CU key and the XCD of each workgroup's record (``gpupool.ops.atomics`` is the
+    twin of all of them); "dumpCU"
+    names the CU it ran on and "dumpSimds" the SIMD of each of its waves. ``hooks``: atomBlocksPerCU,
+    atomLayers, atomSeed, requireAllCUs, atomTimeKernels (adds "marchMs" and "verifyMs", each kernel's time),
+    injectAtomSkip=[layer, op, step, lane], injectAtomFlip=[layer,
+    op, step, lane, bit], injectAtomFaultXcc, injectAtomFaultWorkgroup."""
+    import numpy as np
+
+    from . import atomics as twin
+    if not hasattr(lib(), "mi355x_probe_atomics"):
+        raise RuntimeError("libmi355x_probe.so predates the atomic-unit check: rebuild it")
+    opts = {**({"atomIters": int(iters)} if iters is not None else {}), **{k: _hook(v) for k, v in hooks.items()}}
+    buf, n = None, 0
+    if want_stage:
+        opts["atomDumpStage"] = int(want_stage)
+        n = twin.DUMP_BYTES
+        buf = ctypes.create_string_buffer(n)
+    res = _take(lib().mi355x_probe_atomics(dev, json.dumps(opts).encode(), buf, n))
+    if buf is not None and "dumpCU" in res:
+        w = np.frombuffer(buf.raw, dtype="<u4").copy()
+        res["ldsTable"] = w[twin.DUMP_LDS:twin.DUMP_LDS_DIGEST]
+        res["ldsTable16"] = w[twin.DUMP_LDS16:twin.DUMP_WORDS]
+        res["ldsDigests"] = w[twin.DUMP_LDS_DIGEST:twin.DUMP_L2_DIGEST].reshape(twin.WAVES, twin.LANES)
+        res["l2Digests"] = w[twin.DUMP_L2_DIGEST:twin.DUMP_REGION].reshape(twin.WAVES, twin.LANES)
+        res["region"] = w[twin.DUMP_REGION:twin.DUMP_DEV]
+        res["devRows"] = w[twin.DUMP_DEV:twin.DUMP_RECORDS].reshape(twin.DEV_ROWSETS, twin.ROWSET_WORDS)
+        res["wgKeys"] = w[twin.DUMP_RECORDS:twin.DUMP_RECORDS + int(res["workgroups"])].tolist()
+        res["wgXcc"] = [k >> 8 for k in res["wgKeys"]]
     return res
 
 

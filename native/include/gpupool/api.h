@@ -68,6 +68,7 @@ struct Mi355xPoolSpec {
   double probe_min_host_link_gbps = 0;
   bool probe_lds_check = false;  // spec.probe.ldsCheck: per-CU LDS march and address test (opt-in)
   bool probe_alu_check = false;  // spec.probe.aluCheck: per-SIMD vector-ALU instruction program (opt-in)
+  bool probe_atomics_check = false;  // spec.probe.atomicsCheck: LDS, L2 and device-scope atomic units (opt-in)
   bool probe_register_check = false;  // spec.probe.registerCheck: per-SIMD vector register file march (opt-in)
   double probe_min_hbm_gbps = 0;     // performance floors (0 = off)
   double probe_min_mfma_tflops = 0;

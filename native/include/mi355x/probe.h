@@ -151,6 +151,54 @@ char* mi355x_probe_regs(int device, const char* opts_json, void* image, size_t i
  * last step land in dump (the first min(dump_bytes, 6144) bytes), and the report names "dumpCU" and
  * "dumpSimds" as mi355x_probe_regs does. A bad device: {"passed":false,"error":...}. */
 char* mi355x_probe_alu(int device, const char* opts_json, void* dump, size_t dump_bytes);
+/* Atomic units (opt-in): "atomCheck":1 in mi355x_probe_run's options runs a fixed program of read-modify-write
+ * instructions on every CU: atom_march, 256-thread workgroups with ordinary register counts, "atomBlocksPerCU" of
+ * them per CU (1..16), "atomIters" steps (1..64) per layer, then atom_verify on the same stream. "atomLayers" is
+ * a mask (default 7): 1 lds — the CU's LDS atomic unit, a table in LDS the four waves contend on, returning ops
+ * on words private to a lane with a digest of everything returned, a second addressing slot = lane & 15 that
+ * puts four lanes of every wave on one word (a fault there is slot 64 + (lane & 15)), and a ticket test under
+ * full contention; 2 l2
+ * — the same program through global atomics at agent scope on a region private to the workgroup; 4 dev — the
+ * contended ops on nine row-sets, one every workgroup hits and one per XCD. Ops (a fault's "firstBadOp"): 0 add,
+ * 1 sub, 2 and, 3 or, 4 xor, 5 umin, 6 umax, 7 smin, 8 smax, 9 add_f32, 10 pk_add_f16, 11 pk_add_bf16, 12 add_x2,
+ * 13 umax_x2, 14 xor_x2, 15 add_f64, 16 max_f64 (contended, slot = lane), 17 add_rtn, 18 inc, 19 dec, 20 swap,
+ * 21 cas (returning, not in the dev layer), 22 ticket, 23 returns (a lane's digest; slot = wave * 64 + lane).
+ * Every operand is derived from pattern_word(layer << 40 | op << 32 | step << 10 | part << 8 | wave << 6 | lane,
+ * seed) as native/src/probe/atomics_ref.h documents; floating-point operands are small integers, so every
+ * partial sum in every arrival order is exact. The seed is 0x41544D00 + device ("atomSeed" overrides it) and is
+ * not salted per run: the library computes the expectation on the host once per context and (seed, iters).
+ * atom_verify compares every final value and stores every word's initial value back. The phase rides the MFMA
+ * stream behind every other phase there ("atomFirst":1 ahead of the MFMA phase), with "overlap":0 last on the
+ * one stream. The report then gains, after "alu",
+ *   "atomics":{"ok","iters","layers","workgroups","wgPerXcd","cusTested","cusVerified","perXcd","badCUs",
+ *              "badWorkgroups","ldsBadSlots","l2BadSlots","devBadSlots","badReturns","ticketFaults","firstBadCU",
+ *              "firstBadLayer","firstBadOp","firstBadSlot","firstBadXcc","ms"}
+ * wgPerXcd: the workgroups that ran on XCD 0..7, workgroups their sum. cusTested: CUs a workgroup ran on;
+ * badCUs: CUs a workgroup with an lds or l2 mismatch, a bad digest or a ticket fault ran on; cusVerified = tested
+ * and not bad, perXcd those per XCD. *BadSlots count slots (4 or 8 bytes) off the expectation, badReturns lanes
+ * whose digest is, ticketFaults workgroups whose ticket word is not 256 or whose map is not all ones.
+ * firstBad* name the lowest (layer, op, slot, row) or are null; firstBadCU is the 11-bit CU key (null in the dev
+ * layer), firstBadXcc the CU's XCD, in the dev layer the row's XCD, 8 for the row every workgroup hits. ok = every
+ * count 0 and, unless "requireAllCUs":0, cusVerified = CUs; "passed" also needs it. Without the option: no
+ * "atomics" key, no launch, allocation or event. Test hooks (any, or the dump below, selects the kernel's test
+ * instantiation; all strike wave 0): "injectAtomSkip":[layer, op, step, lane] does not issue that atomic (op 22:
+ * the ticket add), (layer 3 in a hook:
+ * the lds layer's second addressing), "injectAtomFlip":[layer, op, step, lane, bit] flips one bit of the raw operand (bits to 63 for
+ * ops 12..16; for the floating-point ops in the integer, before conversion), "injectAtomFaultXcc":x /
+ * "injectAtomFaultWorkgroup":w only on XCD x / in workgroup w; a value out of range switches a hook off.
+ *
+ * mi355x_probe_atomics: the phase alone, on the device's first stream, under the device's probe lock; the
+ * "atomics" block (after "device" and "passed") is the whole report. opts as above (without "atomCheck"). With
+ * dump and "atomDumpStage":1|2, workgroup 0's data lands in dump (the first min(dump_bytes, 96256) bytes,
+ * uint32): its LDS region [2688] and its lds and l2 digests [4][64] each, as they stood after step 0 (1) or
+ * after the last step (2) — the run goes on after a stage-1 dump and is verified in full — then, of the
+ * whole run, its private region [2688] and the nine dev row-sets [9][1408] as atom_verify read them, the CU key
+ * of every workgroup's record [4096, the first "workgroups" in use; only with the dev layer] and the LDS
+ * row-set of the second addressing [1408, the stage's]; the buffer is zeroed first, so what a layer left out
+ * of "atomLayers" would have written reads 0. With "atomTimeKernels":1 an event is recorded between the two
+ * kernels and the report ends in "marchMs","verifyMs". The report
+ * names "dumpCU" and "dumpSimds" as mi355x_probe_regs does. A bad device: {"passed":false,"error":...}. */
+char* mi355x_probe_atomics(int device, const char* opts_json, void* dump, size_t dump_bytes);
 /* The LDS phase alone, on the device's first stream, under the device's probe lock; the "lds" block (after
  * "device" and "passed") is the whole report. opts as above (without "ldsCheck"). With image and
  * "ldsDumpStage":1|2|3, workgroup 0's LDS is copied out — 1 after the first write, 2 after the first

@@ -87,6 +87,7 @@ Mi355xPoolSpec Mi355xPoolSpec::from(const Json& s) {
   p.probe_lds_check = pr["ldsCheck"].as_bool(false);
   p.probe_register_check = pr["registerCheck"].as_bool(false);
   p.probe_alu_check = pr["aluCheck"].as_bool(false);
+  p.probe_atomics_check = pr["atomicsCheck"].as_bool(false);
   p.probe_min_hbm_gbps = pr["minHbmGBps"].as_double(0);
   p.probe_min_mfma_tflops = pr["minMfmaTflops"].as_double(0);
   p.probe_recheck_seconds = pr["recheckSeconds"].as_int(0);
@@ -125,6 +126,7 @@ Json Mi355xPoolSpec::probe_json() const {
   if (probe_lds_check) j["ldsCheck"] = true;  // absent when off, likewise
   if (probe_register_check) j["registerCheck"] = true;
   if (probe_alu_check) j["aluCheck"] = true;
+  if (probe_atomics_check) j["atomicsCheck"] = true;
   j["minHbmGBps"] = probe_min_hbm_gbps;
   j["minMfmaTflops"] = probe_min_mfma_tflops;
   j["recheckSeconds"] = probe_recheck_seconds;
@@ -362,6 +364,8 @@ std::vector<std::string> validate_mi355x(const Json& obj) {
     errs.push_back("spec.probe.registerCheck: must be of type boolean");
   if (pr.contains("aluCheck") && !pr["aluCheck"].is_bool())
     errs.push_back("spec.probe.aluCheck: must be of type boolean");
+  if (pr.contains("atomicsCheck") && !pr["atomicsCheck"].is_bool())
+    errs.push_back("spec.probe.atomicsCheck: must be of type boolean");
   if (pr.contains("hostLinkBytes")) {
     const int64_t b = pr["hostLinkBytes"].is_int() ? pr["hostLinkBytes"].as_int(0) : 0;
     if (b < (1LL << 20) || b > (1LL << 30)) errs.push_back("spec.probe.hostLinkBytes: must be within [1MiB, 1GiB]");

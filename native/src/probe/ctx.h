@@ -76,6 +76,22 @@ struct DeviceCtx {
   uint32_t alu_exp_seed = 0;
   int alu_exp_iters = 0;        // 0: nothing uploaded yet
   void* alu_dump = nullptr;     // device uint32[4][6][64] (mi355x_probe_alu with a dump buffer)
+  // atomic-unit phase ("atomCheck"): events, counter sets and pinned result as the LDS phase's.
+  // atom_mem is one allocation for atom_wgs workgroups: their private regions, the nine dev
+  // row-sets and the records; made by the first probe that asks, grown for a larger grid, never
+  // shrunk. atom_verify leaves every word at its op's identity, so a run needs no memset.
+  // atom_exp holds the host's expectation (atomics_ref.h kExpWords) of (atom_exp_seed, atom_exp_iters).
+  hipEvent_t atom_ev[3] = {};  // [2]: between the two kernels, recorded only for "atomTimeKernels"
+  unsigned long long* atom_cnt = nullptr;  // device, 2 sets
+  unsigned long long* atom_res = nullptr;  // pinned copy of the set a run used
+  int atom_set = 0;
+  bool atom_clean = false;
+  uint32_t* atom_mem = nullptr;  // device
+  int atom_wgs = 0;              // the grid atom_mem was sized for
+  uint32_t* atom_exp = nullptr;  // device
+  uint32_t atom_exp_seed = 0;
+  int atom_exp_iters = 0;        // 0: nothing uploaded yet
+  uint32_t* atom_dump = nullptr;  // device uint32[kDumpWords] (mi355x_probe_atomics with a dump buffer)
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;

@@ -396,6 +396,108 @@ struct Plan {
 
 }  // namespace alu
 
+namespace atom {
+
+constexpr int kPlanLayers = 3;   // lds, l2, dev (atomics_ref.h kLayers)
+constexpr int kPlanOps = 22;     // contended 0..16, returning 17..21 (atomics_ref.h kAllOps)
+constexpr int kPlanTicket = 22;  // the LDS ticket test as a skip hook's op (atomics_ref.h kTicket)
+constexpr int kPlanWideFirst = 12, kPlanWideEnd = 17;  // the 8-byte ops: a flip's bit runs to 63
+constexpr int kPlanLanes = 64;
+constexpr size_t kPlanDumpWords = 24064;  // atomics_ref.h kDumpWords
+constexpr size_t kDumpBytes = kPlanDumpWords * 4;
+// Steps per layer ("atomIters" selects per run, 1..kMaxIters). The rule that chose aluIters: the largest
+// count at which the phase adds no more to the claim probe's p50 (1 GiB, 2048^3, overlapped) than the
+// register check's recorded +0.060 ms, in two runs. Measured on the MI355X at 1 workgroup per CU, each
+// step count alternating with the plain probe for 40 rounds (scripts/atomics_claim_probe_cost.py,
+// profiles/atomics_claim_probe_cost.json and _run2.json), added p50 in the two runs: 1 step +0.020 /
+// +0.019 ms, 2 +0.037 / +0.037, 4 +0.095 / +0.093, 8 +0.228 / +0.231, 16 +0.50, 32 +1.06, 64 +2.17. 2 is
+// the largest count within the budget in both runs. The two kernels alone take 0.068 ms at 1 step and
+// 0.034 ms per further step (2.24 ms at 64): the dev layer's rows are hit by every workgroup, which is what
+// the steps cost. From 2 steps on the returning ops see values other than the initial ones.
+constexpr int kIters = 2;
+constexpr int kMaxIters = 64;  // bounds the floating-point rows' sums (atomics_ref.h kMaxSumF32)
+// Workgroups per CU of the grid ("atomBlocksPerCU" selects per run, 1..kMaxBlocksPerCU). The kernel owns
+// nothing (74 VGPRs, 16 KiB of LDS), so coverage is per CU and rests on the dispatcher. Same
+// measurement, 400 runs per factor and setting in each of the two runs, the factors interleaved, at 1 step:
+// 1, 2, 4, 8 and 16 all verified 256 CUs in every run, alone on the GPU and inside the overlapped claim
+// probe at either position. The default is the smallest factor, 1: kernels' p50 alone 0.069 ms against
+// 0.118 / 0.218 / 0.423 / 0.830 at 2 / 4 / 8 / 16, claim probe 0.797 ms against 0.826 / 0.921 / 1.129 /
+// 1.534 behind the MFMA phase. Coverage stays part of ok.
+constexpr int kBlocksPerCU = 1;
+constexpr int kMaxBlocksPerCU = 16;
+constexpr int kLayerMask = 7;  // "atomLayers": bit 0 lds, 1 l2, 2 dev
+// Where the phase sits on the MFMA stream ("atomFirst" selects per run): 0 behind the MFMA and
+// low-precision phases and every other opt-in phase, 1 ahead of the MFMA phase. Same measurement, 40
+// alternating rounds at 1 step, in the two runs: behind +0.022 / +0.018 ms, ahead +0.017 / +0.023: the two
+// places change order between the runs and differ by less than a run does from the next, so the default
+// stays where the ALU phase measured cheaper, behind. Not measured at the default of 2 steps.
+constexpr int kFirst = 0;
+constexpr uint32_t kPlanSeedBase = 0x41544D00u;  // atomics_ref.h kSeedBase
+
+// What one run of the phase does (options of mi355x_probe_run with "atomCheck" and of mi355x_probe_atomics).
+struct Plan {
+  bool on = false;  // false: the phase is off
+  int iters = kIters;
+  int blocks_per_cu = kBlocksPerCU;
+  int layers = kLayerMask;
+  // "atomSeed", else kPlanSeedBase + dev: fixed per device and never salted per run, because the
+  // host's expectation table is computed once per (seed, iters) and cached in the context
+  uint32_t seed = 0;
+  // test hooks, each off (-1) when out of range; both strike wave 0 of the struck workgroups
+  int skip_layer = -1, skip_op = -1, skip_step = -1, skip_lane = -1;               // "injectAtomSkip":[layer, op, step, lane]
+  int flip_layer = -1, flip_op = -1, flip_step = -1, flip_lane = -1, flip_bit = 0;  // "injectAtomFlip":[layer, op, step, lane, bit]
+  int fault_xcc = -1;  // "injectAtomFaultXcc": the hooks only on that XCD
+  int fault_wg = -1;   // "injectAtomFaultWorkgroup": the hooks only in that workgroup
+  int dump_stage = 0;  // "atomDumpStage" 1 | 2, only with a caller buffer
+  bool time_kernels = false;  // "atomTimeKernels": an event between the two kernels (mi355x_probe_atomics only)
+  // the test instantiation of the kernel runs only when a hook or the dump asks for it
+  bool test_kernel() const { return skip_layer >= 0 || flip_layer >= 0 || dump_stage != 0; }
+  static Plan parse(const char* json, int dev) {
+    Plan pl;
+    pl.on = true;
+    pl.iters = static_cast<int>(std::min<long long>(kMaxIters, std::max(1LL, opt_int(json, "atomIters", kIters))));
+    pl.blocks_per_cu =
+        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "atomBlocksPerCU", kBlocksPerCU))));
+    const long long layers = opt_int(json, "atomLayers", kLayerMask);
+    pl.layers = layers >= 1 && layers <= kLayerMask ? static_cast<int>(layers) : kLayerMask;
+    const long long seed = opt_int(json, "atomSeed", -1);
+    pl.seed = seed >= 0 ? static_cast<uint32_t>(seed) : kPlanSeedBase + static_cast<uint32_t>(dev);
+    pl.time_kernels = opt_bool(json, "atomTimeKernels", false);
+    const long long stage = opt_int(json, "atomDumpStage", 0);
+    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    // which (layer, op) pairs exist: the returning ops and the ticket test not in the dev layer
+    // layer 3 in a hook: the lds layer's second addressing (slot = lane & 15), contended ops only
+    auto known = [](long long layer, long long op, bool ticket_ok) {
+      if (layer < 0 || layer > kPlanLayers || op < 0) return false;
+      if (op == kPlanTicket) return ticket_ok && layer == 0;
+      return op < (layer >= 2 ? kPlanWideEnd : kPlanOps);
+    };
+    long long f[5];
+    if (opt_ints(json, "injectAtomSkip", f, 4) && known(f[0], f[1], true) && f[2] >= 0 && f[2] < pl.iters && f[3] >= 0 &&
+        f[3] < kPlanLanes) {
+      pl.skip_layer = static_cast<int>(f[0]);
+      pl.skip_op = static_cast<int>(f[1]);
+      pl.skip_step = static_cast<int>(f[2]);
+      pl.skip_lane = static_cast<int>(f[3]);
+    }
+    if (opt_ints(json, "injectAtomFlip", f, 5) && known(f[0], f[1], false) && f[2] >= 0 && f[2] < pl.iters && f[3] >= 0 &&
+        f[3] < kPlanLanes && f[4] >= 0 && f[4] < (f[1] >= kPlanWideFirst && f[1] < kPlanWideEnd ? 64 : 32)) {
+      pl.flip_layer = static_cast<int>(f[0]);
+      pl.flip_op = static_cast<int>(f[1]);
+      pl.flip_step = static_cast<int>(f[2]);
+      pl.flip_lane = static_cast<int>(f[3]);
+      pl.flip_bit = static_cast<int>(f[4]);
+    }
+    const long long xcc = opt_int(json, "injectAtomFaultXcc", -1);
+    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
+    const long long wg = opt_int(json, "injectAtomFaultWorkgroup", -1);
+    pl.fault_wg = wg >= 0 && wg < kMaxBlocksPerCU * 256 ? static_cast<int>(wg) : -1;
+    return pl;
+  }
+};
+
+}  // namespace atom
+
 // Where the GEMM fault hooks corrupt C (test hooks "injectGemmFaultRow" / "injectGemmFaultCol"):
 // -1 is the element the hooks always took, row n/3 and column n/5; any other value outside [0, n)
 // means no fault, like "injectFlipAtChunk".
@@ -455,6 +557,8 @@ struct ProbeOptions {
   bool regs_first = regs::kFirst == 1;  // "regsFirst": as "ldsFirst"
   alu::Plan alu;                   // "aluCheck"; !on: off, and none of its options is looked up
   bool alu_first = alu::kFirst == 1;  // "aluFirst": as "ldsFirst"
+  atom::Plan atom;                 // "atomCheck"; !on: off, and none of its options is looked up
+  bool atom_first = atom::kFirst == 1;  // "atomFirst": as "ldsFirst"
 
   static ProbeOptions parse(const char* json, int dev = 0) {
     ProbeOptions o;
@@ -506,6 +610,12 @@ struct ProbeOptions {
       o.alu = alu::Plan::parse(json, dev);
       o.alu.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_alu
       o.alu_first = opt_int(json, "aluFirst", alu::kFirst) == 1;
+    }
+    if (opt_bool(json, "atomCheck", false)) {
+      o.atom = atom::Plan::parse(json, dev);
+      o.atom.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_atomics
+      o.atom.time_kernels = false;  // the claim probe records no event between the kernels
+      o.atom_first = opt_int(json, "atomFirst", atom::kFirst) == 1;
     }
     return o;
   }

@@ -34,6 +34,7 @@
 //   lds.h            per-CU LDS march and address test ("ldsCheck")
 //   regfile.h        per-SIMD vector register file march ("regCheck")
 //   alu.h            per-SIMD vector-ALU instruction program ("aluCheck"); alu_ref.h its host expectation
+//   atomics.h        LDS, L2 and device-scope atomic units ("atomCheck"); atomics_ref.h its host expectation
 //   ctx.h            per-device state and ensure_ctx(); peer.h the xGMI checks; sweep.h the HBM sweep
 //   sweep_window.h   a sweep window split over the buffer's chunks (pure host, unit-tested)
 #include <hip/hip_runtime.h>
@@ -57,6 +58,7 @@
 #include "mfma_phase.h"
 #include "options.h"
 #include "alu.h"
+#include "atomics.h"
 #include "regfile.h"
 #include "peer.h"
 #include "report.h"
@@ -195,6 +197,8 @@ std::string run_probe(int dev, const char* opts) {
   if (rg.on) regs::ensure(ctx, rg.test_kernel(), false);
   alu::Plan al = o.alu;
   if (al.on) alu::ensure(ctx, al, false);
+  atom::Plan at = o.atom;
+  if (at.on) atom::ensure(ctx, at, false);
   ProbeReport rep;
   PhaseTimes& t = rep.phases;
   t.hbm_first = o.hbm_first;
@@ -214,7 +218,8 @@ std::string run_probe(int dev, const char* opts) {
   // never gets a stream of its own: ahead of the MFMA phase on s2, where it overlaps the first HBM
   // fill ("ldsFirst":0 behind it and the low-precision phase), or serial, last on the one stream.
   // The register-file phase ("regCheck", "regsFirst") takes the same places, behind the LDS phase,
-  // and the vector-ALU phase ("aluCheck", "aluFirst") behind the register-file phase
+  // and the vector-ALU phase ("aluCheck", "aluFirst") behind the register-file phase, the
+  // atomic-unit phase ("atomCheck", "atomFirst") behind the vector-ALU phase
   auto t_run = std::chrono::steady_clock::now();
   reset_counters(ctx, o, cnt, s, s2);
   const lowp::Phase lp = lowp_phase(ctx, o, base, lay);
@@ -236,16 +241,24 @@ std::string run_probe(int dev, const char* opts) {
     alu::launch(ctx, s2, al);
     alu_pending = false;
   };
+  bool atom_pending = at.on;
+  auto enqueue_atom = [&](bool here) {
+    if (!atom_pending || !here) return;
+    atom::launch(ctx, s2, at);
+    atom_pending = false;
+  };
   auto enqueue_mfma = [&](int when) {
     if (!o.mfma || o.hbm_first != when) return;
     enqueue_lds(o.overlap && o.lds_first);
     enqueue_regs(o.overlap && o.regs_first);
     enqueue_alu(o.overlap && o.alu_first);
+    enqueue_atom(o.overlap && o.atom_first);
     launch_mfma_phase(base, lay, o, ctx, s2);
     lowp::launch(s2, lp);
     enqueue_lds(o.overlap);
     enqueue_regs(o.overlap);
     enqueue_alu(o.overlap);
+    enqueue_atom(o.overlap);
   };
   const PatternPass pass = hbm_pass(ctx, o, dev, base, lay, n16);
   enqueue_mfma(0);
@@ -254,6 +267,7 @@ std::string run_probe(int dev, const char* opts) {
   enqueue_lds(true);  // serial, or no MFMA phase to follow
   enqueue_regs(true);
   enqueue_alu(true);
+  enqueue_atom(true);
   if (hl.n16) hostlink::launch(ctx, hl_s, hl);
   t.launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
 
@@ -282,6 +296,11 @@ std::string run_probe(int dev, const char* opts) {
   if (al.on) {
     if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
     rep.alu = alu::finish(ctx, al, o.require_all_cus);
+  }
+  rep.has_atom = at.on;
+  if (at.on) {
+    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
+    rep.atom = atom::finish(ctx, at, o.require_all_cus);
   }
   rep.lowp = lowp::finish(lp, o.require_all_cus);
   t.mfma_wall_ms = o.mfma ? ms_since(t_run) : 0.0;
@@ -829,6 +848,25 @@ char* mi355x_probe_alu(int dev, const char* opts_json, void* dump, size_t dump_b
       PROBE_CHECK(hipMemcpy(dump, ctx.alu_dump, std::min<size_t>(dump_bytes, alu::kDumpBytes), hipMemcpyDeviceToHost));
     // the block is the whole report, with the usual head
     return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + alu_block(r).substr(1);
+  });
+}
+
+char* mi355x_probe_atomics(int dev, const char* opts_json, void* dump, size_t dump_bytes) {
+  if (!device_ok(dev)) return bad_device();
+  ProbeActive active;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded(device_head(dev), [&] {
+    atom::Plan pl = atom::Plan::parse(opts_json, dev);
+    if (!dump || !dump_bytes) pl.dump_stage = 0;
+    DeviceCtx& ctx = ensure_ctx(dev);
+    atom::ensure(ctx, pl, pl.dump_stage != 0);
+    atom::launch(ctx, ctx.stream, pl);
+    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
+    const AtomResult r = atom::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
+    if (pl.dump_stage)
+      PROBE_CHECK(hipMemcpy(dump, ctx.atom_dump, std::min<size_t>(dump_bytes, atom::kDumpBytes), hipMemcpyDeviceToHost));
+    // the block is the whole report, with the usual head
+    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + atom_block(r).substr(1);
   });
 }
 

@@ -1,5 +1,5 @@
 // mi355x-probe CLI: `mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma]
-// [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--lds-check] [--register-check] [--alu-check] [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
+// [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--lds-check] [--register-check] [--alu-check] [--atomics-check] [--list]`. Prints one JSON object per probed device and exits 0 iff every probe passed.
 // Equivalent of the reference's in-pod `nvidia-smi` smoke check (GPU调度平台搭建.md:134-138),
 // but it exercises HBM and the matrix cores instead of only enumerating the device.
 #include <algorithm>
@@ -22,6 +22,7 @@ int main(int argc, char** argv) {
   bool lds_check = false;   // "ldsCheck": the per-CU LDS phase
   bool reg_check = false;   // "regCheck": the per-SIMD register-file phase
   bool alu_check = false;   // "aluCheck": the per-SIMD vector-ALU phase
+  bool atom_check = false;  // "atomCheck": the atomic-unit phase
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -64,10 +65,12 @@ int main(int argc, char** argv) {
       reg_check = true;
     } else if (a == "--alu-check") {
       alu_check = true;
+    } else if (a == "--atomics-check") {
+      atom_check = true;
     } else if (a == "--list") {
       list = true;
     } else if (a == "-h" || a == "--help") {
-      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--lds-check] [--register-check] [--alu-check] [--list]\n");
+      std::printf("usage: mi355x-probe [--device N|--all] [--hbm-bytes B] [--gemm-n N] [--no-mfma] [--low-precision fp8,mxfp8,mxfp4] [--host-link-bytes N] [--lds-check] [--register-check] [--alu-check] [--atomics-check] [--list]\n");
       return 0;
     } else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
@@ -110,6 +113,7 @@ int main(int argc, char** argv) {
   if (lds_check) opts_s += ",\"ldsCheck\":1";
   if (reg_check) opts_s += ",\"regCheck\":1";
   if (alu_check) opts_s += ",\"aluCheck\":1";
+  if (atom_check) opts_s += ",\"atomCheck\":1";
   opts_s += "}";
   const char* opts = opts_s.c_str();
   std::vector<std::string> results(devs.size());

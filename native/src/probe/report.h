@@ -280,6 +280,64 @@ inline std::string alu_block(const AluResult& r) {
   return out + "}";
 }
 
+// The atomic-unit phase: which CUs' workgroups ran the whole atomic program with every final value
+// and every returned value as expected. first_bad is atomics_ref.h's fault_key of the lowest
+// mismatch (layer, op, slot, row / XCD, CU key), all-ones = none.
+struct AtomResult {
+  int iters = 0, layers = 0;
+  unsigned long long workgroups = 0;
+  unsigned long long wg_per_xcd[8] = {};
+  int expected = 0;  // CUs of the device
+  int cus_tested = 0, cus_verified = 0, bad_cus = 0;
+  int per_xcd[8] = {};  // verified CUs
+  unsigned long long bad_workgroups = 0, lds_bad_slots = 0, l2_bad_slots = 0, dev_bad_slots = 0, bad_returns = 0,
+                     ticket_faults = 0, first_bad = ~0ull;
+  float ms = 0;
+  bool require_all = true;  // "requireAllCUs"
+  int dump_cu = -1;         // mi355x_probe_atomics with a dump buffer: the CU key of the dumped workgroup
+  int dump_simds[4] = {};   // ... and the SIMD each of its four waves ran on
+  float march_ms = -1, verify_ms = -1;  // mi355x_probe_atomics with "atomTimeKernels": each kernel's time
+  bool ok() const {
+    return !bad_workgroups && !lds_bad_slots && !l2_bad_slots && !dev_bad_slots && !bad_returns && !ticket_faults &&
+           !bad_cus && (!require_all || cus_verified >= expected);
+  }
+};
+
+inline std::string atom_block(const AtomResult& r) {
+  static const char* const kLayerNames[] = {"lds", "l2", "dev"};
+  static const char* const kOpNames[] = {"add", "sub", "and", "or", "xor", "umin", "umax", "smin", "smax", "add_f32",
+                                         "pk_add_f16", "pk_add_bf16", "add_x2", "umax_x2", "xor_x2", "add_f64", "max_f64",
+                                         "add_rtn", "inc", "dec", "swap", "cas", "ticket", "returns"};
+  std::string per = "[", wgs = "[";
+  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
+  for (int x = 0; x < 8; ++x) wgs += (x ? "," : "") + std::to_string(r.wg_per_xcd[x]);
+  const bool none = r.first_bad == ~0ull;
+  const unsigned long long layer = r.first_bad >> 60, op = (r.first_bad >> 52) & 0xFF, slot = (r.first_bad >> 36) & 0xFFFF,
+                           xcc = (r.first_bad >> 32) & 0xF;
+  auto name = [&](const char* const* t, unsigned long long i, unsigned long long n) {
+    return none || i >= n ? std::string("null") : "\"" + std::string(t[i]) + "\"";
+  };
+  std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"iters\":" + std::to_string(r.iters) +
+                    ",\"layers\":" + std::to_string(r.layers) + ",\"workgroups\":" + std::to_string(r.workgroups) +
+                    ",\"wgPerXcd\":" + wgs + "]" + ",\"cusTested\":" + std::to_string(r.cus_tested) +
+                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badWorkgroups\":" + std::to_string(r.bad_workgroups) +
+                    ",\"ldsBadSlots\":" + std::to_string(r.lds_bad_slots) + ",\"l2BadSlots\":" + std::to_string(r.l2_bad_slots) +
+                    ",\"devBadSlots\":" + std::to_string(r.dev_bad_slots) + ",\"badReturns\":" + std::to_string(r.bad_returns) +
+                    ",\"ticketFaults\":" + std::to_string(r.ticket_faults) +
+                    // the dev layer's rows belong to no CU
+                    ",\"firstBadCU\":" + (none || layer == 2 ? std::string("null") : std::to_string(r.first_bad & 0x7FF)) +
+                    ",\"firstBadLayer\":" + name(kLayerNames, layer, 3) + ",\"firstBadOp\":" + name(kOpNames, op, 24) +
+                    ",\"firstBadSlot\":" + (none ? std::string("null") : std::to_string(slot)) +
+                    // lds, l2: the CU's XCD; dev: the row's XCD, 8 for the row every workgroup hits
+                    ",\"firstBadXcc\":" + (none ? std::string("null") : std::to_string(xcc)) + ",\"ms\":" + jnum(r.ms);
+  if (r.dump_cu >= 0)
+    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
+           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  if (r.march_ms >= 0) out += ",\"marchMs\":" + jnum(r.march_ms) + ",\"verifyMs\":" + jnum(r.verify_ms);
+  return out + "}";
+}
+
 // Host wall-clock of a probe's steps.
 struct PhaseTimes {
   bool arena_reused = false;
@@ -299,7 +357,7 @@ inline std::string phases_block(const PhaseTimes& t) {
 inline std::string device_head(int dev) { return "\"device\":" + std::to_string(dev); }
 
 // Everything mi355x_probe_run reports. "cus" only with the MFMA phase, "lowp" only with a dtype,
-// "hostLink", "lds", "regs" and "alu" only when asked for.
+// "hostLink", "lds", "regs", "alu" and "atomics" only when asked for.
 struct ProbeReport {
   int dev = 0;
   std::string uuid, arch;
@@ -315,11 +373,13 @@ struct ProbeReport {
   RegsResult regs;
   bool has_alu = false;
   AluResult alu;
+  bool has_atom = false;
+  AtomResult atom;
   double total_ms = 0;
   PhaseTimes phases;
   bool passed() const {
     bool ok = hbm.ok() && mfma.ok && (!has_host_link || host_link.ok()) && (!has_lds || lds.ok()) &&
-              (!has_regs || regs.ok()) && (!has_alu || alu.ok());
+              (!has_regs || regs.ok()) && (!has_alu || alu.ok()) && (!has_atom || atom.ok());
     for (const LowpResult& l : lowp) ok = ok && l.ok;
     return ok;
   }
@@ -342,6 +402,7 @@ inline std::string probe_report_open(const ProbeReport& r) {
   if (r.has_lds) out += ",\"lds\":" + lds_block(r.lds);
   if (r.has_regs) out += ",\"regs\":" + regs_block(r.regs);
   if (r.has_alu) out += ",\"alu\":" + alu_block(r.alu);
+  if (r.has_atom) out += ",\"atomics\":" + atom_block(r.atom);
   out += ",\"ms\":" + jnum(r.total_ms);
   out += ",\"phases\":" + phases_block(r.phases);
   return out;

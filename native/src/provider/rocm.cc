@@ -101,6 +101,8 @@ Json DeviceView::status_json() const {
       p["regsVerifiedCUs"] = probe.path("regs.cusVerified");
     if (probe["alu"].is_object())  // spec.probe.aluCheck: the CUs whose four SIMDs' vector ALUs tested clean
       p["aluVerifiedCUs"] = probe.path("alu.cusVerified");
+    if (probe["atomics"].is_object())  // spec.probe.atomicsCheck: the CUs whose atomic units tested clean
+      p["atomicsVerifiedCUs"] = probe.path("atomics.cusVerified");
     s["probe"] = p;
   }
   if (sharing.is_object() && sharing.size()) s["sharing"] = sharing;  // slot isolation (agent slots.py)

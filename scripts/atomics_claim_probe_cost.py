@@ -1,0 +1,224 @@
+#!/usr/bin/env python3
+"""What spec.probe.atomicsCheck needs to cover every CU, what it costs in the claim-time probe at which
+step count, and that the default probe did not move.
+
+(a) ``atomBlocksPerCU`` 1, 2, 4, 8, 16: the atomic-unit phase alone on the GPU (probe.atomics) and inside
+    the overlapped claim probe (probe.run, 1 GiB, gemm_n=2048) at both positions on the MFMA stream
+    ("atomFirst" 0 and 1), ``--runs`` runs each, the factors interleaved, at ``STEPS`` = 1 step whatever the
+    library's default is (the factor and the position are chosen before the step count). Per factor and setting: the
+    minimum and the histogram of cusVerified, the p50 of the two kernels' ms and of the claim probe's
+    ms. The kernel owns nothing (ordinary register counts, 16 KiB of LDS), so coverage is per CU
+    and rests on the dispatcher. The default factor is the smallest one whose every run verified
+    every CU alone and inside the probe at the default position.
+(b) ``atomIters`` 1, 2, 4, ... 64 at the library's default factor and position, each alternating with the
+    claim probe without the phase for ``--rounds`` rounds (one step count at a time: the library keeps one
+    expectation table per context): p50 of the probe's own ms per step count,
+    what the phase adds, and the kernel's time per step (slope of its p50 ms alone on the GPU over
+    the step count). The default is the largest count that adds no more than the register
+    check's recorded +0.060 ms (README, profiles/regs_claim_probe_cost.json).
+(c) Claim probe without the phase, with it behind the MFMA phase ("atomFirst":0) and ahead of it
+    ("atomFirst":1), at ``STEPS`` = 1 step and the default factor, alternating for ``--rounds`` rounds.
+(e) Each of the two kernels timed with an event between them ("atomTimeKernels"), alone on the GPU, at
+    1, 2 and 64 steps, 50 runs each: atom_verify must cost less than atom_march.
+(d) With ``--parent-lib DIR`` (a build of the parent commit's libmi355x_probe.so): child processes
+    that load this tree's library or the parent's, alternating, ``--rounds`` each; a child warms up
+    and reports the p50 of 30 default probes. With ``--parent-lib-copy DIR2`` (a second copy of the
+    same build) the same procedure runs on the parent's library against itself: the difference of
+    that null pair is what a difference must exceed.
+
+    python scripts/atomics_claim_probe_cost.py [--runs 400] [--rounds 40] [--parent-lib DIR [--parent-lib-copy DIR2]] \\
+        > profiles/atomics_claim_probe_cost.json
+"""
+from __future__ import annotations
+
+import argparse
+import collections
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+KW = dict(hbm_bytes=1 << 30, gemm_n=2048)
+FACTORS = (1, 2, 4, 8, 16)
+ITERS = (1, 2, 4, 8, 16, 32, 64)
+BUDGET_MS = 0.060  # what the register check adds (README)
+STEPS = 1  # the step count of (a) and (c)
+med = statistics.median
+COUNTS = ("ldsBadSlots", "l2BadSlots", "devBadSlots", "badReturns", "ticketFaults", "badWorkgroups")
+
+
+def child() -> None:
+    from gpupool.ops import probe
+    probe.init()
+    for _ in range(5):
+        assert probe.run(0, **KW)["passed"]
+    print(json.dumps(med(probe.run(0, **KW)["ms"] for _ in range(30))))
+
+
+def default_path(me: list[str], libs: dict[str, str], rounds: int) -> dict:
+    """``libs``: two names -> library directory ("" = this tree's). Alternating child processes."""
+    a, b = list(libs)
+    ms: dict[str, list[float]] = {a: [], b: []}
+    for r in range(rounds):
+        for which in ((a, b) if r % 2 == 0 else (b, a)):
+            env = dict(os.environ)
+            if libs[which]:
+                env["GPUPOOL_NATIVE_DIR"] = os.path.abspath(libs[which])
+            # each child is one GPU step with its own limit; a failing child ends the script
+            p = subprocess.run(me + ["--child"], env=env, capture_output=True, text=True, timeout=120, check=True)
+            ms[which].append(float(p.stdout.strip().splitlines()[-1]))
+        if (r + 1) % 10 == 0:
+            print(f"default path {a} vs {b}: round {r + 1}/{rounds}", file=sys.stderr, flush=True)
+    return {"what": "p50 over child processes of each child's p50 probe ms (30 default probes)",
+            f"{a}_ms": round(med(ms[a]), 4), f"{b}_ms": round(med(ms[b]), 4),
+            f"{b}_even_rounds_ms": round(med(ms[b][0::2]), 4),
+            f"{b}_odd_rounds_ms": round(med(ms[b][1::2]), 4),
+            "difference_ms": round(med(ms[a]) - med(ms[b]), 4),
+            "odd_even_spread_ms": round(abs(med(ms[b][0::2]) - med(ms[b][1::2])), 4)}
+
+
+def sweep(probe, cus: int, runs: int) -> dict:
+    alone = {f: {"verified": [], "ms": []} for f in FACTORS}
+    inside = {first: {f: {"verified": [], "ms": [], "probe_ms": []} for f in FACTORS} for first in (0, 1)}
+    for r in range(runs):
+        for f in (FACTORS if r % 2 == 0 else FACTORS[::-1]):
+            a = probe.atomics(0, iters=STEPS, atomBlocksPerCU=f, requireAllCUs=0)
+            assert not any(a[k] for k in COUNTS) and a["workgroups"] == f * cus, a
+            alone[f]["verified"].append(a["cusVerified"])
+            alone[f]["ms"].append(a["ms"])
+        for first in (0, 1):
+            for f in (FACTORS if r % 2 == 0 else FACTORS[::-1]):
+                p = probe.run(0, atom_check=True, atomIters=STEPS, atomBlocksPerCU=f, atomFirst=first, requireAllCUs=0, **KW)
+                assert not any(p["atomics"][k] for k in COUNTS) and p["hbm"]["ok"] and p["mfma"]["ok"], p
+                inside[first][f]["verified"].append(p["atomics"]["cusVerified"])
+                inside[first][f]["ms"].append(p["atomics"]["ms"])
+                inside[first][f]["probe_ms"].append(p["ms"])
+        if (r + 1) % 50 == 0:
+            print(f"sweep: run {r + 1}/{runs}", file=sys.stderr, flush=True)
+
+    def fold(d: dict) -> dict:
+        out = {"min_cus_verified": min(d["verified"]),
+               "runs_short_of_every_cu": sum(v < cus for v in d["verified"]),
+               "cus_verified_histogram": dict(sorted(collections.Counter(d["verified"]).items())),
+               "atomics_ms_p50": round(med(d["ms"]), 4)}
+        if "probe_ms" in d:
+            out["claim_probe_ms_p50"] = round(med(d["probe_ms"]), 4)
+        return out
+    names = {0: "inside_the_claim_probe_behind_the_mfma_phase", 1: "inside_the_claim_probe_ahead_of_the_mfma_phase"}
+    res = {"runs": runs, "cus": cus, "steps": STEPS, "alone": {str(f): fold(alone[f]) for f in FACTORS}}
+    for first in (0, 1):
+        res[names[first]] = {str(f): fold(inside[first][f]) for f in FACTORS}
+        full = [f for f in FACTORS
+                if min(alone[f]["verified"]) == cus and min(inside[first][f]["verified"]) == cus]
+        res["smallest_factor_with_every_cu_in_every_run_atomFirst_%d" % first] = full[0] if full else None
+    return res
+
+
+def alternate(probe, sets: list, rounds: int) -> tuple[dict, dict, dict]:
+    """Alternating rounds over option sets (name, kwargs): the probe's ms, the kernel's ms, the runs not ok."""
+    for _, kw in sets:
+        for _ in range(3):
+            assert probe.run(0, **kw, **KW)["hbm"]["ok"]
+    t: dict = {k: [] for k, _ in sets}
+    kernel: dict = {k: [] for k, kw in sets if kw}
+    short = {k: 0 for k, kw in sets if kw}
+    for r in range(rounds):
+        for k, kw in (sets if r % 2 == 0 else sets[::-1]):
+            res = probe.run(0, **kw, **KW)
+            assert res["hbm"]["ok"] and res["mfma"]["ok"], res
+            t[k].append(res["ms"])
+            if kw:
+                assert not any(res["atomics"][k] for k in COUNTS), res
+                kernel[k].append(res["atomics"]["ms"])
+                short[k] += 0 if res["atomics"]["ok"] else 1
+    return t, kernel, short
+
+
+def iters_cost(probe, rounds: int) -> dict:
+    # one step count at a time against the plain probe: the library keeps ONE expectation table per
+    # context, so alternating step counts would recompute it on the host inside every probe's clock,
+    # which a pool (one step count for its lifetime) never does
+    p50, added, kernel, short, none = {}, {}, {}, {}, []
+    for n in ITERS:
+        t, k, s = alternate(probe, [("none", {}), (str(n), {"atom_check": True, "atomIters": n})], rounds)
+        none += t["none"]
+        p50[str(n)] = round(med(t[str(n)]), 4)
+        added[str(n)] = round(med(t[str(n)]) - med(t["none"]), 4)
+        kernel.update(k)
+        short.update(s)
+    t = {"none": none}
+    p50["none"] = round(med(none), 4)
+    alone = {n: med(probe.atomics(0, iters=n)["ms"] for _ in range(15)) for n in ITERS}
+    fits = [n for n in ITERS if added[str(n)] <= BUDGET_MS]
+    return {"rounds": rounds, "budget_ms": BUDGET_MS, "claim_probe_ms_p50": p50, "added_ms_p50": added,
+            "none_even_odd_rounds_ms": [round(med(t["none"][0::2]), 4), round(med(t["none"][1::2]), 4)],
+            "atomics_kernels_ms_beside_the_probe_p50": {k: round(med(v), 4) for k, v in kernel.items()},
+            "atomics_kernels_ms_alone_p50": {str(n): round(v, 4) for n, v in alone.items()},
+            "kernel_us_per_step_alone": round((alone[ITERS[-1]] - alone[ITERS[0]]) / (ITERS[-1] - ITERS[0]) * 1e3, 4),
+            "largest_count_within_budget": max(fits) if fits else None,
+            "runs_short_of_coverage": short}
+
+
+def position_cost(probe, rounds: int) -> dict:
+    sets = [("none", {}), ("atomics behind the MFMA phase", {"atom_check": True, "atomIters": STEPS, "atomFirst": 0}),
+            ("atomics ahead of the MFMA phase", {"atom_check": True, "atomIters": STEPS, "atomFirst": 1})]
+    t, kernel, short = alternate(probe, sets, rounds)
+    p50 = {k: round(med(v), 4) for k, v in t.items()}
+    return {"rounds": rounds, "steps": STEPS, "claim_probe_ms_p50": p50,
+            "added_ms_p50": {k: round(v - p50["none"], 4) for k, v in p50.items() if k != "none"},
+            "none_even_odd_rounds_ms": [round(med(t["none"][0::2]), 4), round(med(t["none"][1::2]), 4)],
+            "atomics_kernels_ms_beside_the_probe_p50": {k: round(med(v), 4) for k, v in kernel.items()},
+            "runs_short_of_coverage_at_the_defaults": short}
+
+
+def kernel_split(probe) -> dict:
+    out = {}
+    for n in (1, 2, 64):
+        rs = [probe.atomics(0, iters=n, atomTimeKernels=1) for _ in range(50)]
+        assert all(r["passed"] for r in rs), rs[0]
+        out[str(n)] = {"atom_march_ms_p50": round(med(r["marchMs"] for r in rs), 4),
+                       "atom_verify_ms_p50": round(med(r["verifyMs"] for r in rs), 4),
+                       "both_ms_p50": round(med(r["ms"] for r in rs), 4)}
+    return {"what": "each kernel alone on the GPU, an event between them, 50 runs per step count", "by_steps": out}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=400)
+    ap.add_argument("--rounds", type=int, default=40)
+    ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--parent-lib-copy", default="", help="a second copy of the parent's build: the null pair")
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--default-path-only", action="store_true", help="only (d)")
+    a = ap.parse_args()
+    if a.child:
+        return child()
+    out: dict = {"probe": "hbmBytes 1 GiB x 2 patterns, gemmN 2048, two streams"}
+    me = [sys.executable, os.path.abspath(__file__)]
+    if a.parent_lib:  # children first: this process has not touched the GPU yet
+        out["default_path"] = default_path(me, {"this": "", "parent": a.parent_lib}, a.rounds)
+        if a.parent_lib_copy:
+            out["default_path_null_pair"] = default_path(me, {"parent_copy": a.parent_lib_copy, "parent": a.parent_lib},
+                                                         a.rounds)
+    if a.default_path_only:
+        from gpupool.ops import probe  # after the children: this process touches the GPU only now
+        probe.init()
+        out["kernel_split"] = kernel_split(probe)
+        print(json.dumps(out, indent=1))
+        return
+    from gpupool.ops import probe
+    probe.init()
+    cus = int(probe.identify(0)["computeUnits"])
+    out["blocks_per_cu_sweep"] = sweep(probe, cus, a.runs)
+    out["iters_cost"] = iters_cost(probe, a.rounds)
+    out["position_cost"] = position_cost(probe, a.rounds)
+    out["kernel_split"] = kernel_split(probe)
+    probe.trim(0)
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    main()

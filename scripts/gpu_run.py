@@ -114,6 +114,11 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # alu_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
         # A/B and its null pair)
         "alu": [("alu_claim_probe_cost", [PY, "scripts/alu_claim_probe_cost.py"], 600, {})],
+        # spec.probe.atomicsCheck: the grid factor that covers every CU, the cheaper position, the step count
+        # that fits the register check's +0.060 ms and the phase's cost in the claim probe (give
+        # atomics_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
+        # A/B and its null pair)
+        "atomics": [("atomics_claim_probe_cost", [PY, "scripts/atomics_claim_probe_cost.py"], 600, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],
