@@ -11,11 +11,17 @@ as ``pattern_word(index(g, t, o, lane), seed) ^ h`` with ``h`` as it stood when 
 every result ``r``, as bits: ``h = (rotl(h, 5) ^ r) * 0x9E3779B1``. Floating-point operands take sign and
 mantissa from the word and a biased exponent in a window at the bias (f32 and f64 2^-4..2^4, f16
 2^-2..2^2), so every result is finite and only f16 results reach the subnormal range. The ``trans`` group
-has no expectation (the device compares it with its own consensus).
+has no expected digest (the device compares it with its own consensus, ``wave_value``): hardware
+approximations are not bit-defined. For it the module holds a reference of the nine functions instead
+(``trans_operands``, ``trans_reference``) and the comparer of a raw-result trace (``probe.alu(...,
+want_stage=3)``) against it within per-function error bounds (``trace_chain_errors``,
+``trace_accuracy``); that part uses float64 (``math``), ``Fraction`` and ``math.isqrt``.
 """
 from __future__ import annotations
 
 import functools
+import math
+import struct
 from fractions import Fraction
 
 import numpy as np
@@ -27,6 +33,10 @@ WAVES = 4  # of a workgroup
 SEED_BASE = 0x414C5500  # the phase's seed is SEED_BASE + HIP device ordinal
 FOLD_MUL = 0x9E3779B1
 DUMP_BYTES = WAVES * len(GROUPS) * LANES * 4
+TRACE_STEPS, TRACE_WORDS = 64, 12  # dump stage 3: uint32 [wave][step][word][lane], word 0 the digest as the step began
+TRACE_BYTES = WAVES * TRACE_STEPS * TRACE_WORDS * LANES * 4
+WAVE_MUL = 0x9E3779B97F4A7C15
+M64 = 0xFFFFFFFFFFFFFFFF
 WRITE_LANE = 5
 SWIZZLE_XOR = 0x15
 M32 = 0xFFFFFFFF
@@ -271,6 +281,174 @@ def _expected(seed: int, steps: int) -> tuple:
 
 def expected(seed: int, steps: int) -> np.ndarray:
     """uint32 [6][64] (group, lane): every lane's digests after ``steps`` steps — the kernel's dump stage 1
-    is ``steps`` = 1, stage 2 and the verdict ``steps`` = iters. Row 5 (``trans``) is zero: it has no
-    expectation. Computed once per (seed, steps)."""
+    is ``steps`` = 1, stage 2 and the verdict ``steps`` = iters. Row 5 (``trans``) is zero: its digest
+    hashes hardware approximations and has no expected value; what the group computes is checked from
+    the stage-3 trace against ``trans_reference`` below. Computed once per (seed, steps)."""
     return np.array(_expected(int(seed) & M32, int(steps)), dtype=np.uint32)
+
+
+# ------------------------------------------------------------------ trans: the reference of the nine functions
+# The trace's result words 1..11 in step_trans's order, and the function each belongs to.
+TRANS_FUNCS = ("exp2", "log2", "rcp", "rsq", "sqrt", "sin", "cos", "rcp_f64", "rsq_f64")
+TRANS_WORDS = ("exp2", "log2", "rcp", "rsq", "sqrt", "sin", "cos", "rcp_f64.lo", "rcp_f64.hi", "rsq_f64.lo", "rsq_f64.hi")
+LOG_FLOOR = 2.0 ** -10  # a log2 result below this is judged in units of ulp32(LOG_FLOOR), not of its own ULP
+TRIG_UNIT = 2.0 ** -24  # sin and cos are judged in absolute units: their accuracy is absolute near the zeros
+
+
+# A test bound may hide no planted defect: it is at most a quarter of the error of a flipped bit 8 of an f32
+# result word (256 units; for sin and cos on results of magnitude >= 0.5) and of bit 40 of an f64 result.
+TRANS_CAPS = {**{f: 64 for f in TRANS_FUNCS[:7]}, "rcp_f64": 2 ** 38, "rsq_f64": 2 ** 38}
+
+
+def bound_from_measured(max_error: float) -> int:
+    """A test bound from a measured maximum error, in the function's units: the maximum x 4 (a sample of
+    operands does not reach an approximation's worst case), rounded up to a power of two."""
+    return 1 << max(0, math.ceil(math.log2(4.0 * max_error))) if max_error > 0 else 1
+
+
+def f32_value(bits: int) -> float:
+    """The f32 of this encoding, as a Python float (exact)."""
+    return struct.unpack("<f", struct.pack("<I", bits & M32))[0]
+
+
+def f64_value(bits: int) -> float:
+    return struct.unpack("<d", struct.pack("<Q", bits & M64))[0]
+
+
+def wave_value(digests) -> int:
+    """The 64-bit value a wave publishes for the consensus, from its 64 lanes' trans digests: the sum over
+    lanes of h * (0x9E3779B97F4A7C15 + 2 * lane) mod 2^64, with 0 (the empty slot) mapped to 1."""
+    assert len(digests) == LANES
+    v = sum(int(h) * (WAVE_MUL + 2 * lane) for lane, h in enumerate(digests)) & M64
+    return v or 1
+
+
+def trans_operand_bits(hs: int, step: int, lane: int, seed: int) -> tuple[int, int, int]:
+    """The encodings of step_trans's operands: f32 a, f32 b, f64 q."""
+    w = _words(5, step, 4, lane, seed, hs)
+    return f32_bits(w[0]), f32_bits(w[1]), f64_bits(w[2], w[3])
+
+
+def trans_operands(hs: int, step: int, lane: int, seed: int) -> tuple[float, float, float]:
+    """(a, b, q) of step ``step`` of the trans group in ``lane``, ``hs`` the lane's digest as the step began.
+    Python floats hold an f32 and an f64 exactly."""
+    ab, bb, qb = trans_operand_bits(hs, step, lane, seed)
+    return f32_value(ab), f32_value(bb), f64_value(qb)
+
+
+def _turns(x: float) -> float:
+    """x revolutions as radians of the reduced argument: r = x - round(x) is exact for an f32 x."""
+    return 2.0 * math.pi * (x - round(x))
+
+
+def rsqrt_fraction(q: Fraction, bits: int = 128) -> Fraction:
+    """1 / sqrt(q) for q > 0 with at least ``bits`` - 8 > 100 correct bits, from one integer square root:
+    isqrt(2^(2 bits) / q) / 2^bits, for q in the operand window [2^-4, 2^4)."""
+    n = (q.denominator << (2 * bits)) // q.numerator
+    return Fraction(math.isqrt(n), 1 << bits)
+
+
+def trans_reference(a: float, b: float, q: float) -> tuple:
+    """The true values of what step_trans computes, in its order: exp2(a), log2|b|, 1/a, 1/sqrt|b|, sqrt|a|,
+    sin(2 pi a), cos(2 pi b) as float64 (v_sin_f32 and v_cos_f32 take revolutions; the argument is reduced
+    exactly first), then 1/q as the exact Fraction and 1/sqrt|q| as a Fraction good to > 100 bits."""
+    fb = abs(b)
+    qf = Fraction(q)
+    return (2.0 ** a, math.log2(fb), 1.0 / a, 1.0 / math.sqrt(fb), math.sqrt(abs(a)), math.sin(_turns(a)),
+            math.cos(_turns(b)), 1 / qf, rsqrt_fraction(abs(qf)))
+
+
+def _floor_log2(x) -> int:
+    """floor(log2 |x|) of a non-zero float or Fraction, exactly."""
+    f = Fraction(x)
+    f = -f if f < 0 else f
+    e = f.numerator.bit_length() - f.denominator.bit_length()
+    return e - 1 if Fraction(2) ** e > f else e
+
+
+def trans_unit(func: str, ref) -> Fraction:
+    """The unit the error of ``func`` is counted in at the reference value ``ref``: the f32 ULP at ``ref`` for
+    exp2, log2 (never below the ULP at LOG_FLOOR), rcp, rsq and sqrt; 2^-24 for sin and cos; the f64 ULP
+    at ``ref`` for the two f64 functions."""
+    if func in ("sin", "cos"):
+        return Fraction(TRIG_UNIT)
+    if func in ("rcp_f64", "rsq_f64"):
+        return Fraction(2) ** (_floor_log2(ref) - 52)
+    if func == "log2" and abs(ref) < LOG_FLOOR:
+        return Fraction(2) ** (_floor_log2(LOG_FLOOR) - 23)
+    return Fraction(2) ** (_floor_log2(ref) - 23)
+
+
+def trans_results(words) -> list[int]:
+    """A step's eleven result words -> the nine results' encodings (the f64 halves joined, low word first)."""
+    w = [int(x) for x in words]
+    return w[:7] + [w[7] | (w[8] << 32), w[9] | (w[10] << 32)]
+
+
+def trans_error(func: str, got_bits: int, ref) -> tuple[float | None, str]:
+    """(error in ``trans_unit`` units, what else is wrong) of a result encoding against its reference:
+    the error is None and the text non-empty for a result that is not finite; the text also names a wrong
+    sign (judged where the reference is at least one unit away from zero)."""
+    f64 = func.endswith("_f64")
+    exp_all_ones = (got_bits >> 52) & 0x7FF == 0x7FF if f64 else (got_bits >> 23) & 0xFF == 0xFF
+    if exp_all_ones:
+        return None, "not finite"
+    got = Fraction(f64_value(got_bits) if f64 else f32_value(got_bits))
+    r = Fraction(ref)
+    unit = trans_unit(func, ref)
+    err = float(abs(got - r) / unit)
+    negative = bool(got_bits >> (63 if f64 else 31))
+    wrong_sign = abs(r) >= unit and negative != (r < 0)
+    return err, "wrong sign" if wrong_sign else ""
+
+
+def trace_chain_errors(trace, steps: int) -> list[str]:
+    """The exact properties of one wave's trace uint32 [TRACE_STEPS][12][64]: the digest starts at 0, each
+    step's stored digest is the fold of the step before, and the steps past ``steps`` are zero. -> what
+    does not hold ([] when all does)."""
+    t = np.asarray(trace, dtype=np.uint32)
+    assert t.shape == (TRACE_STEPS, TRACE_WORDS, LANES), t.shape
+    n = min(int(steps), TRACE_STEPS)
+    out = []
+    if t[0, 0].any():
+        out.append(f"hs[0] is not zero in lane(s) {np.flatnonzero(t[0, 0])[:4].tolist()}")
+    for s in range(n - 1):
+        for lane in np.flatnonzero(trace_fold(t, s) != t[s + 1, 0])[:4].tolist():
+            out.append(f"hs[{s + 1}] is not the fold of step {s} in lane {lane}")
+    if t[n:].any():
+        out.append(f"steps {n}..{TRACE_STEPS - 1} are not zero")
+    return out
+
+
+def trace_fold(trace, step: int) -> np.ndarray:
+    """uint32 [64]: every lane's digest after ``step``: the fold of its eleven words from its stored hs."""
+    t = np.asarray(trace, dtype=np.uint32)
+    return np.array([_fold_all(int(t[step, 0, lane]), [int(x) for x in t[step, 1:, lane]]) for lane in range(LANES)],
+                    dtype=np.uint32)
+
+
+def trace_samples(trace, steps: int, seed: int):
+    """Every result of one wave's trace with its reference: yields (func, step, lane, operand encodings
+    (a, b, q), got encoding, reference value). The operands come from the stored digest of each step."""
+    t = np.asarray(trace, dtype=np.uint32)
+    for s in range(min(int(steps), TRACE_STEPS)):
+        for lane in range(LANES):
+            ops = trans_operand_bits(int(t[s, 0, lane]), s, lane, seed)
+            refs = trans_reference(f32_value(ops[0]), f32_value(ops[1]), f64_value(ops[2]))
+            for func, got, ref in zip(TRANS_FUNCS, trans_results(t[s, 1:, lane]), refs):
+                yield func, s, lane, ops, got, ref
+
+
+def trace_accuracy(trace, steps: int, seed: int, bounds: dict) -> list[str]:
+    """Every result of one wave's trace against ``trans_reference`` at the operands its stored digests give:
+    finite, the right sign, and within ``bounds[func]`` units (``trans_unit``). -> one line per failure,
+    naming function, seed, step, lane, operand bits, got, want and the error in units."""
+    out = []
+    for func, s, lane, ops, got, ref in trace_samples(trace, steps, seed):
+        err, why = trans_error(func, got, ref)
+        if err is None or why or err > bounds[func]:
+            width = 16 if func.endswith("_f64") else 8
+            out.append(f"{func} seed {seed:#x} step {s} lane {lane}: a {ops[0]:#010x} b {ops[1]:#010x} q {ops[2]:#018x} "
+                       f"got {got:#0{width + 2}x} want {float(ref)!r}: "
+                       + (why if err is None else f"{why + ', ' if why else ''}error {err:.4g} units, bound {bounds[func]}"))
+    return out

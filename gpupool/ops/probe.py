@@ -288,7 +288,12 @@ def alu(dev: int, iters: int | None = None, want_stage: int = 0, **hooks) -> dic
     library's). -> the "alu" block of ``run`` plus "device" and "passed". ``want_stage`` 1 | 2:
     workgroup 0's digests after step 0 / after the last step come back under "data" (uint32
     [4][6][64]: wave, group, lane; ``gpupool.ops.alu`` is the exact twin of the first five groups),
-    "dumpCU" names the CU it ran on and "dumpSimds" the SIMD of each of its waves. ``hooks``:
+    "dumpCU" names the CU it ran on and "dumpSimds" the SIMD of each of its waves. ``want_stage`` 3:
+    "data" is workgroup 0's trace of the trans group instead, uint32 [4][64][12][64] (wave, step, word,
+    lane) of the first min(iters, 64) steps and zero past them: word 0 the lane's digest as the step
+    began, words 1..11 the step's results as they were folded (``gpupool.ops.alu.TRANS_WORDS``; the
+    probe itself judges trans by consensus only, the tests compare this trace with
+    ``gpupool.ops.alu.trans_reference``). ``hooks``:
     aluBlocksPerCU, aluSeed, requireAllCUs, injectAluFlip=[group, step, lane, bit],
     injectAluFaultSimd, injectAluFaultXcc."""
     import numpy as np
@@ -298,13 +303,16 @@ def alu(dev: int, iters: int | None = None, want_stage: int = 0, **hooks) -> dic
         raise RuntimeError("libmi355x_probe.so predates the vector-ALU check: rebuild it")
     opts = {**({"aluIters": int(iters)} if iters is not None else {}), **{k: _hook(v) for k, v in hooks.items()}}
     buf, n = None, 0
+    shape = (twin.WAVES, len(twin.GROUPS), twin.LANES)
     if want_stage:
         opts["aluDumpStage"] = int(want_stage)
         n = twin.DUMP_BYTES
+        if int(want_stage) == 3:
+            n, shape = twin.TRACE_BYTES, (twin.WAVES, twin.TRACE_STEPS, twin.TRACE_WORDS, twin.LANES)
         buf = ctypes.create_string_buffer(n)
     res = _take(lib().mi355x_probe_alu(dev, json.dumps(opts).encode(), buf, n))
     if buf is not None and "dumpCU" in res:
-        res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(twin.WAVES, len(twin.GROUPS), twin.LANES).copy()
+        res["data"] = np.frombuffer(buf.raw, dtype="<u4").reshape(shape).copy()
     return res
 
 

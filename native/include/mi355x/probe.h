@@ -149,7 +149,14 @@ char* mi355x_probe_regs(int device, const char* opts_json, void* image, size_t i
  * block (after "device" and "passed") is the whole report. opts as above (without "aluCheck"). With dump and
  * "aluDumpStage":1|2, workgroup 0's digests uint32[4][6][64] (wave, group, lane) after step 0 / after the
  * last step land in dump (the first min(dump_bytes, 6144) bytes), and the report names "dumpCU" and
- * "dumpSimds" as mi355x_probe_regs does. A bad device: {"passed":false,"error":...}. */
+ * "dumpSimds" as mi355x_probe_regs does. "aluDumpStage":3 returns workgroup 0's raw-result trace of the
+ * transcendental group instead, uint32[4][64][12][64] (wave, step, word, lane; the first min(dump_bytes, 786432)
+ * bytes), from a device buffer of its own that is zeroed ahead of the launch: the first min(iters, 64) steps, word 0
+ * the lane's trans digest as the step began, words 1..11 the step's results exactly as they were folded (the
+ * "injectAluFlip" XOR included): exp2(a), log2|b|, rcp(a), rsq|b|, sqrt|a|, sin(a), cos(b), rcp(q) low, high,
+ * rsq|q| low, high; "dumpCU" and "dumpSimds" as for the other stages. The probe's verdict on that group stays the
+ * consensus; the trace is what the test suite compares with a reference of the nine functions. A bad device:
+ * {"passed":false,"error":...}. */
 char* mi355x_probe_alu(int device, const char* opts_json, void* dump, size_t dump_bytes);
 /* Atomic units (opt-in): "atomCheck":1 in mi355x_probe_run's options runs a fixed program of read-modify-write
  * instructions on every CU: atom_march, 256-thread workgroups with ordinary register counts, "atomBlocksPerCU" of

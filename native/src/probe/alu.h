@@ -36,8 +36,13 @@
 //
 // alu_march<true> is the test instantiation, launched only when a hook or the dump is asked for: it
 // XORs one bit into the last result of one step of one group in one lane (of every wave, of one
-// SIMD's or one XCD's waves) and stores workgroup 0's digests after step 0 or after the last step.
-// alu_march<false>, the production instantiation, carries none of it.
+// SIMD's or one XCD's waves) and stores workgroup 0's digests after step 0 or after the last step
+// (dump stages 1 and 2) or, stage 3, the trans group's raw results: per wave, step (the first
+// kTraceSteps) and lane the digest as the step began and the step's eleven result words exactly as
+// they were folded, the hook's XOR included. The probe judges trans by consensus only; the trace is
+// what lets the test suite compare the program with a reference of the nine functions
+// (gpupool/ops/alu.py trans_reference). alu_march<false>, the production instantiation, carries none
+// of it.
 //
 // What it cannot find: a defect of the transcendental unit common to every SIMD of the device; the
 // scalar ALU; opcodes outside the groups; defects that show only at other data, clocks or
@@ -85,10 +90,11 @@ struct KernelArgs {
   int flip_group;
   uint32_t flip_step, flip_lane, flip_bit;
   int fault_simd, fault_xcc;  // the flip only on this SIMD / XCD (< 0: on all)
-  int dump_stage;             // 1 | 2: workgroup 0 stores its digests after step 0 / after the last step
+  int dump_stage;             // 1 | 2: workgroup 0 stores its digests after step 0 / after the last step; 3: the trans trace
   uint32_t* dump;             // [4][kGroups][kLanes]
   unsigned long long* cnt;    // this run's counter set
   unsigned long long* next;   // the next run's, reset here
+  uint32_t* trace;            // stage 3: [4][kTraceSteps][kTraceWords][kLanes]; last, so no other argument moves
 };
 
 // ------------------------------------------------------------------ one-instruction helpers
@@ -308,16 +314,35 @@ __device__ __forceinline__ void step(uint32_t hs, uint32_t t, uint32_t lane, uin
   else step_trans(hs, t, lane, seed, flip, f);
 }
 
-// One group's loop: the digest after ``iters`` steps; ``first`` gets the digest after step 0.
+// One group's loop: the digest after ``iters`` steps; ``first`` gets the digest after step 0. ``trace``
+// (test instantiation, trans group, else null): this thread's word 0 of step 0 of its wave's trace.
 template <int kGroup, bool kTest>
-__device__ __forceinline__ uint32_t run_group(const KernelArgs& a, uint32_t lane, uint32_t fmask, uint32_t* first) {
+__device__ __forceinline__ uint32_t run_group(const KernelArgs& a, uint32_t lane, uint32_t fmask, uint32_t* first,
+                                              uint32_t* trace = nullptr) {
+  constexpr bool kTraced = kTest && kGroup == kTrans;
   uint32_t h = 0;
 #pragma unroll 1
   for (int t = 0; t < a.iters; ++t) {
     uint32_t flip = 0;
     if constexpr (kTest) flip = a.flip_group == kGroup && static_cast<uint32_t>(t) == a.flip_step ? fmask : 0u;
     const uint32_t hs = h;
-    step<kGroup>(hs, static_cast<uint32_t>(t), lane, a.seed, flip, [&](uint32_t r) { h = fold(h, r); });
+    uint32_t* row = nullptr;  // the next word of this step's [kTraceWords][kLanes]
+    if constexpr (kTraced) {
+      if (trace && t < kTraceSteps) {
+        row = trace + static_cast<size_t>(t) * kTraceWords * kLanes;
+        *row = hs;
+        row += kLanes;
+      }
+    }
+    step<kGroup>(hs, static_cast<uint32_t>(t), lane, a.seed, flip, [&](uint32_t r) {
+      h = fold(h, r);
+      if constexpr (kTraced) {
+        if (row) {
+          *row = r;
+          row += kLanes;
+        }
+      }
+    });
     if constexpr (kTest)
       if (t == 0) *first = h;
   }
@@ -344,7 +369,10 @@ __global__ __launch_bounds__(kThreads) void alu_march(const KernelArgs a) {
   h[kF64] = run_group<kF64, kTest>(a, lane, fmask, &first[kF64]);
   h[kF16] = run_group<kF16, kTest>(a, lane, fmask, &first[kF16]);
   h[kLane] = run_group<kLane, kTest>(a, lane, fmask, &first[kLane]);
-  h[kTrans] = run_group<kTrans, kTest>(a, lane, fmask, &first[kTrans]);
+  uint32_t* trace = nullptr;
+  if constexpr (kTest)
+    if (b == 0 && a.dump_stage == 3) trace = a.trace + static_cast<size_t>(wave) * kTraceSteps * kTraceWords * kLanes + lane;
+  h[kTrans] = run_group<kTrans, kTest>(a, lane, fmask, &first[kTrans], trace);
 
   // ---- exact groups against the host's table: the lowest group that differs in this lane
   uint32_t bad_group = ~0u;
@@ -356,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void alu_march(const KernelArgs a) {
   // (CU key << 32) | SIMD << 16 | group << 8 | lane of the lowest mismatch
   uint64_t key = bad ? (static_cast<uint64_t>(k) << 32) | (simd << 16) | (bad_group << 8) | lane : ~0ull;
   // ---- trans: the wave's 64 digests as one 64-bit value (a sum, so the butterfly's order is free)
-  uint64_t tv = static_cast<uint64_t>(h[kTrans]) * (0x9E3779B97F4A7C15ull + 2ull * lane);
+  uint64_t tv = wave_term(h[kTrans], lane);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     key = umin64(key, static_cast<uint64_t>(__shfl_xor(static_cast<unsigned long long>(key), off, 64)));
@@ -365,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void alu_march(const KernelArgs a) {
   if (tv == 0) tv = 1;  // 0 is the empty slot
 
   if constexpr (kTest) {
-    if (b == 0 && a.dump_stage) {
+    if (b == 0 && (a.dump_stage == 1 || a.dump_stage == 2)) {
 #pragma unroll
       for (int g = 0; g < kGroups; ++g)
         a.dump[(wave * kGroups + g) * kLanes + lane] = a.dump_stage == 1 ? first[g] : h[g];
@@ -405,11 +433,11 @@ __global__ __launch_bounds__(kThreads) void alu_march(const KernelArgs a) {
 }
 
 // ------------------------------------------------------------------ the phase: ensure / launch / finish
-// Makes the phase's events, counter sets, pinned result and expectation table (and, ``want_dump``,
-// the device copy of one workgroup's digests), puts both counter sets at their reset values unless
-// the last run left them so, and computes and uploads the host's expectation when (seed, steps)
-// is not the pair the table holds. All of it ahead of the probe's clock.
-inline void ensure(DeviceCtx& c, const Plan& pl, bool want_dump) {
+// Makes the phase's events, counter sets, pinned result and expectation table (and, ``dump_stage``
+// 1 | 2, the device copy of one workgroup's digests, 3, of its trans trace), puts both counter sets
+// at their reset values unless the last run left them so, and computes and uploads the host's
+// expectation when (seed, steps) is not the pair the table holds. All of it ahead of the probe's clock.
+inline void ensure(DeviceCtx& c, const Plan& pl, int dump_stage) {
   if (!c.alu_res) {  // set last: a failure half way is picked up by the next probe that asks
     for (auto& e : c.alu_ev)
       if (!e) PROBE_CHECK(hipEventCreate(&e));
@@ -439,7 +467,8 @@ inline void ensure(DeviceCtx& c, const Plan& pl, bool want_dump) {
     c.alu_exp_seed = pl.seed;
     c.alu_exp_iters = pl.iters;
   }
-  if (want_dump && !c.alu_dump) PROBE_CHECK(hipMalloc(&c.alu_dump, kDumpBytes));
+  if ((dump_stage == 1 || dump_stage == 2) && !c.alu_dump) PROBE_CHECK(hipMalloc(&c.alu_dump, kDumpBytes));
+  if (dump_stage == 3 && !c.alu_trace) PROBE_CHECK(hipMalloc(&c.alu_trace, kTraceBytes));
 }
 
 // Enqueues the phase on stream s: an event, the kernel, an event, the counters' copy. No host synchronise.
@@ -454,12 +483,16 @@ inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
   a.flip_bit = pl.flip_group >= 0 ? static_cast<uint32_t>(pl.flip_bit) : 0u;
   a.fault_simd = pl.fault_simd;
   a.fault_xcc = pl.fault_xcc;
-  a.dump_stage = c.alu_dump ? pl.dump_stage : 0;
+  // a stage without its buffer (a probe, which has no caller buffer) is off
+  a.dump_stage = (pl.dump_stage == 3 ? c.alu_trace : c.alu_dump) ? pl.dump_stage : 0;
   a.dump = static_cast<uint32_t*>(c.alu_dump);
+  a.trace = static_cast<uint32_t*>(c.alu_trace);
   a.cnt = c.alu_cnt + c.alu_set * kSlots;
   a.next = c.alu_cnt + (c.alu_set ^ 1) * kSlots;
   const int grid = pl.blocks_per_cu * c.prop.multiProcessorCount;
   c.alu_clean = false;  // until finish() has seen this run end
+  // the trace holds the first min(iters, kTraceSteps) steps; what the run does not write reads as zero
+  if (a.dump_stage == 3) PROBE_CHECK(hipMemsetAsync(c.alu_trace, 0, kTraceBytes, s));
   PROBE_CHECK(hipEventRecord(c.alu_ev[0], s));
   if (pl.test_kernel()) hipLaunchKernelGGL(alu_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(alu_march<false>, dim3(grid), dim3(kThreads), 0, s, a);

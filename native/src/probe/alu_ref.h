@@ -15,7 +15,9 @@
 // (exact for + and * of floats); f16 and bf16 are computed in double, where every intermediate of
 // the window is exact, and rounded once by round_to(). The dot products get small integers, so
 // every partial sum is exact whatever the order. The transcendental group has no host
-// expectation: the device checks it by consensus.
+// expectation in the probe: the device checks it by consensus (wave_value is that value's host side),
+// and the test suite compares the kernel's trace of it (alu.h, dump stage 3) with a reference of the
+// nine functions (gpupool/ops/alu.py trans_reference).
 #pragma once
 
 #include <algorithm>
@@ -78,6 +80,9 @@ ALU_HD int small_int(uint32_t w, int i) { return static_cast<int>((w >> (4 * i))
 ALU_HD int small_acc(uint32_t w) { return 256 + static_cast<int>((w >> 16) & 255u); }
 // the lane v_readlane reads in step t
 ALU_HD uint32_t read_lane(uint32_t step) { return (7u * step + 37u) & 63u; }
+// A wave's 64 trans digests as the one 64-bit value the consensus compares: the sum over lanes of
+// these terms mod 2^64 (a sum, so the order is free), 0 (the empty slot) mapped to 1.
+ALU_HD uint64_t wave_term(uint32_t h, uint32_t lane) { return static_cast<uint64_t>(h) * (0x9E3779B97F4A7C15ull + 2ull * lane); }
 
 // ------------------------------------------------------------------ host side
 
@@ -265,6 +270,13 @@ inline void step_lane(uint32_t* h, uint32_t t, uint32_t seed, uint32_t* trace = 
     f(y[0]);                                          // v_readfirstlane_b32
     h[l] = f.h;
   }
+}
+
+// the consensus value of a wave whose lanes hold the trans digests h[0..63] (alu.h sums in a butterfly)
+inline uint64_t wave_value(const uint32_t* h) {
+  uint64_t v = 0;
+  for (uint32_t l = 0; l < kLanes; ++l) v += wave_term(h[l], l);
+  return v ? v : 1;
 }
 
 // expect[g][lane], g < kExactGroups: the digests after ``steps`` steps (the kernel's dump stage 1

@@ -76,6 +76,7 @@ struct DeviceCtx {
   uint32_t alu_exp_seed = 0;
   int alu_exp_iters = 0;        // 0: nothing uploaded yet
   void* alu_dump = nullptr;     // device uint32[4][6][64] (mi355x_probe_alu with a dump buffer)
+  void* alu_trace = nullptr;    // device uint32[4][64][12][64] (... with "aluDumpStage":3: the trans trace)
   // atomic-unit phase ("atomCheck"): events, counter sets and pinned result as the LDS phase's.
   // atom_mem is one allocation for atom_wgs workgroups: their private regions, the nine dev
   // row-sets and the records; made by the first probe that asks, grown for a larger grid, never

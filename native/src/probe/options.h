@@ -323,6 +323,10 @@ constexpr int kPlanLanes = 64;
 constexpr int kSimdsPerCU = 4;
 // workgroup 0's digests as mi355x_probe_alu copies them out: uint32 [wave][group][lane]
 constexpr size_t kDumpBytes = static_cast<size_t>(kSimdsPerCU) * kPlanGroups * kPlanLanes * 4;
+// workgroup 0's trace of the trans group (dump stage 3): uint32 [wave][step][word][lane], the first
+// kTraceSteps steps; word 0 is the digest as the step began, words 1..11 the step's results as folded
+constexpr int kTraceSteps = 64, kTraceWords = 12;
+constexpr size_t kTraceBytes = static_cast<size_t>(kSimdsPerCU) * kTraceSteps * kTraceWords * kPlanLanes * 4;
 // Steps per group ("aluIters" selects per run): the largest power of two at which the phase adds no
 // more to the claim probe's p50 (1 GiB, 2048^3, overlapped) than the register check's recorded +0.060 ms.
 // Measured on the MI355X at 1 workgroup per CU, each step count alternating with the plain probe for
@@ -365,7 +369,7 @@ struct Plan {
   int flip_group = -1, flip_step = -1, flip_lane = -1, flip_bit = -1;  // "injectAluFlip":[group, step, lane, bit]
   int fault_simd = -1;                                                 // "injectAluFaultSimd": the flip only on that SIMD
   int fault_xcc = -1;                                                  // "injectAluFaultXcc": the flip only on that XCD
-  int dump_stage = 0;                                                  // "aluDumpStage" 1 | 2, only with a caller buffer
+  int dump_stage = 0;                                                  // "aluDumpStage" 1 | 2 | 3, only with a caller buffer
   // the test instantiation of the kernel runs only when a hook or the dump asks for it
   bool test_kernel() const { return flip_group >= 0 || dump_stage != 0; }
   static Plan parse(const char* json, int dev) {
@@ -389,9 +393,11 @@ struct Plan {
     const long long xcc = opt_int(json, "injectAluFaultXcc", -1);
     pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
     const long long stage = opt_int(json, "aluDumpStage", 0);
-    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    pl.dump_stage = stage >= 1 && stage <= 3 ? static_cast<int>(stage) : 0;
     return pl;
   }
+  // what the caller's buffer receives: the digests (stages 1 and 2) or the trans trace (stage 3)
+  size_t dump_bytes() const { return dump_stage == 3 ? kTraceBytes : dump_stage ? kDumpBytes : 0; }
 };
 
 }  // namespace alu

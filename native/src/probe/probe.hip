@@ -196,7 +196,7 @@ std::string run_probe(int dev, const char* opts) {
   regs::Plan rg = o.regs;
   if (rg.on) regs::ensure(ctx, rg.test_kernel(), false);
   alu::Plan al = o.alu;
-  if (al.on) alu::ensure(ctx, al, false);
+  if (al.on) alu::ensure(ctx, al, 0);
   atom::Plan at = o.atom;
   if (at.on) atom::ensure(ctx, at, false);
   ProbeReport rep;
@@ -840,12 +840,13 @@ char* mi355x_probe_alu(int dev, const char* opts_json, void* dump, size_t dump_b
     alu::Plan pl = alu::Plan::parse(opts_json, dev);
     if (!dump || !dump_bytes) pl.dump_stage = 0;
     DeviceCtx& ctx = ensure_ctx(dev);
-    alu::ensure(ctx, pl, pl.dump_stage != 0);
+    alu::ensure(ctx, pl, pl.dump_stage);
     alu::launch(ctx, ctx.stream, pl);
     PROBE_CHECK(hipStreamSynchronize(ctx.stream));
     const AluResult r = alu::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
     if (pl.dump_stage)
-      PROBE_CHECK(hipMemcpy(dump, ctx.alu_dump, std::min<size_t>(dump_bytes, alu::kDumpBytes), hipMemcpyDeviceToHost));
+      PROBE_CHECK(hipMemcpy(dump, pl.dump_stage == 3 ? ctx.alu_trace : ctx.alu_dump, std::min<size_t>(dump_bytes, pl.dump_bytes()),
+                            hipMemcpyDeviceToHost));
     // the block is the whole report, with the usual head
     return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + alu_block(r).substr(1);
   });

@@ -114,6 +114,10 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # alu_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
         # A/B and its null pair)
         "alu": [("alu_claim_probe_cost", [PY, "scripts/alu_claim_probe_cost.py"], 600, {})],
+        # the accuracy of the transcendental opcodes on the phase's operands, from the kernel's trans trace:
+        # the figures the bounds of tests/gpu/test_probe_alu_trans_gpu.py come from (the script writes
+        # profiles/alu_trans_accuracy.json itself)
+        "alu-trans": [("alu_trans_accuracy", [PY, "scripts/alu_trans_accuracy.py"], 300, {})],
         # spec.probe.atomicsCheck: the grid factor that covers every CU, the cheaper position, the step count
         # that fits the register check's +0.060 ms and the phase's cost in the claim probe (give
         # atomics_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
