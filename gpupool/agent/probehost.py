@@ -49,6 +49,8 @@ import threading
 import time
 from typing import Any
 
+from ..ops.probe_checks import keywords
+
 log = logging.getLogger("gpupool.agent.probehost")
 
 _ctx = None
@@ -152,10 +154,7 @@ class _HipKernel:
                           mfma=bool(a["mfma"]), gemm_n=int(a["gemmN"]), overlap=int(a["overlap"]),
                           mfma_low_precision=tuple(a.get("lowPrecision") or ()),
                           host_link_bytes=int(a.get("hostLinkBytes") or 0),
-                          **({"lds_check": True} if a.get("ldsCheck") else {}),
-                          **({"reg_check": True} if a.get("registerCheck") else {}),
-                          **({"alu_check": True} if a.get("aluCheck") else {}),
-                          **({"atom_check": True} if a.get("atomicsCheck") else {}),
+                          **keywords(a),
                           **{k: int(v) for k, v in (a.get("testHooks") or {}).items()})
         if op == "sweep":
             return hp.hbm_sweep(self.ordinal(a.get("hipUUID")), int(a["offset"]), int(a["bytes"]),

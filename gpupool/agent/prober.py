@@ -32,6 +32,7 @@ import time
 
 from ..api import schema
 from ..ops import native_path
+from ..ops.probe_checks import CHECKS, keywords
 from . import simprobe
 
 log = logging.getLogger("gpupool.agent.prober")
@@ -239,10 +240,8 @@ class Prober:
         # spec.probe.hostLinkCheck: bytes of pinned host memory tested over PCIe (0 = off)
         hostlink = int(opts.get("hostLinkBytes") or schema.DEFAULT_HOST_LINK_BYTES) \
             if opts.get("hostLinkCheck") else 0
-        lds = bool(opts.get("ldsCheck"))  # spec.probe.ldsCheck: the per-CU LDS phase
-        regs = bool(opts.get("registerCheck"))  # spec.probe.registerCheck: the register-file phase
-        alu = bool(opts.get("aluCheck"))  # spec.probe.aluCheck: the vector-ALU phase
-        atomics = bool(opts.get("atomicsCheck"))  # spec.probe.atomicsCheck: the atomic-unit phase
+        # spec.probe.ldsCheck / registerCheck / aluCheck / atomicsCheck: the opt-in per-CU phases
+        checks = [c for c in CHECKS if opts.get(c.spec_key)]
         if self.mode == "off" or not opts.get("enabled", True):
             return {"passed": True, "backend": "off", "ms": 0.0}
         if self.mode == "simulated":
@@ -260,14 +259,7 @@ class Prober:
                 args["lowPrecision"] = lowp
             if hostlink:
                 args["hostLinkBytes"] = hostlink
-            if lds:
-                args["ldsCheck"] = True
-            if regs:
-                args["registerCheck"] = True
-            if alu:
-                args["aluCheck"] = True
-            if atomics:
-                args["atomicsCheck"] = True
+            args.update({c.spec_key: True for c in checks})
             if self.mode == "helper-sim":
                 args.update(dev=dev, opts=opts)
             res = self._helper_call(dev, "probe", args, timeout)
@@ -281,17 +273,12 @@ class Prober:
                 res = self._hip.run(ordinal, hbm_bytes=hbm, mfma=mfma,
                                     gemm_n=self.gemm_n if floors else self.overlap_gemm_n,
                                     overlap=0 if floors else 1, mfma_low_precision=tuple(lowp),
-                                    host_link_bytes=hostlink, **({"lds_check": True} if lds else {}),
-                                    **({"reg_check": True} if regs else {}),
-                                    **({"alu_check": True} if alu else {}),
-                                    **({"atom_check": True} if atomics else {}))
+                                    host_link_bytes=hostlink, **keywords(opts))
             else:
                 cmd = [native_path("mi355x-probe"), "--device", str(ordinal), "--hbm-bytes",
                        str(hbm), "--gemm-n", str(self.gemm_n)] + ([] if mfma else ["--no-mfma"]) + \
                     (["--low-precision", ",".join(lowp)] if lowp else []) + \
-                    (["--host-link-bytes", str(hostlink)] if hostlink else []) + \
-                    (["--lds-check"] if lds else []) + (["--register-check"] if regs else []) + \
-                    (["--alu-check"] if alu else []) + (["--atomics-check"] if atomics else [])
+                    (["--host-link-bytes", str(hostlink)] if hostlink else []) + [c.flag for c in checks]
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 try:
                     res = json.loads(p.stdout.strip().splitlines()[-1])

@@ -52,6 +52,16 @@ def fault(dev: dict, key: str):
     return v if v is not None else (dev.get("faults") or {}).get(key)
 
 
+def _verified_per_xcd(cus: int, bad: int) -> list:
+    """``cus`` CUs spread over the 8 XCDs, less ``bad`` taken from the front, XCD by XCD."""
+    per = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
+    for x in range(8):
+        take = min(bad, per[x])
+        per[x] -= take
+        bad -= take
+    return per
+
+
 def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
     t0 = time.perf_counter()
     hbm = int(opts.get("hbmBytes", 1 << 30))
@@ -98,12 +108,7 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
     if opts.get("ldsCheck"):
         cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
         bad = min(cus, int(fault(dev, "ldsFault") or 0))
-        per = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
-        left = bad
-        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
-            take = min(left, per[x])
-            per[x] -= take
-            left -= take
+        per = _verified_per_xcd(cus, bad)
         res["lds"] = {"ok": bad == 0, "bytesPerCU": 163840, "patterns": 2, "salt": 0,
                       "workgroups": SIM_LDS_BLOCKS_PER_CU * cus, "cusTested": cus,
                       "cusVerified": cus - bad, "perXcd": per, "badCUs": bad, "badBits": bad,
@@ -116,12 +121,7 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
     if opts.get("registerCheck"):
         cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
         bad = min(cus, int(fault(dev, "regFault") or 0))
-        per = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
-        left = bad
-        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
-            take = min(left, per[x])
-            per[x] -= take
-            left -= take
+        per = _verified_per_xcd(cus, bad)
         res["regs"] = {"ok": bad == 0, "registersPerLane": 512, "workgroupsPerCU": 1, "patterns": 2,
                        "salt": 0, "workgroups": SIM_REGS_BLOCKS_PER_CU * cus, "cusTested": cus,
                        "cusVerified": cus - bad, "simdsTested": 4 * cus, "simdShort": 0, "perXcd": per,
@@ -136,12 +136,7 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
     if opts.get("aluCheck"):
         cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
         bad = min(cus, int(fault(dev, "aluFault") or 0))
-        per = [4 * (cus // 8 + (1 if x < cus % 8 else 0)) for x in range(8)]
-        left = 4 * bad
-        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
-            take = min(left, per[x])
-            per[x] -= take
-            left -= take
+        per = [4 * n for n in _verified_per_xcd(cus, bad)]  # SIMDs
         wg = SIM_ALU_BLOCKS_PER_CU * cus
         res["alu"] = {"ok": bad == 0, "iters": SIM_ALU_ITERS, "workgroups": wg, "waves": 4 * wg,
                       "wavesPerSimd": [wg] * 4, "simdsTested": 4 * cus, "simdsVerified": 4 * (cus - bad),
@@ -159,13 +154,7 @@ def probe(dev: dict, opts: dict, sim_ms: float) -> dict:
     if opts.get("atomicsCheck"):
         cus = int((dev.get("asic") or {}).get("computeUnits") or 256)
         bad = min(cus, int(fault(dev, "atomicsFault") or 0))
-        full = [cus // 8 + (1 if x < cus % 8 else 0) for x in range(8)]
-        per = list(full)
-        left = bad
-        for x in range(8):  # the bad CUs are the first ones, XCD by XCD
-            take = min(left, per[x])
-            per[x] -= take
-            left -= take
+        full, per = _verified_per_xcd(cus, 0), _verified_per_xcd(cus, bad)
         wg = SIM_ATOM_BLOCKS_PER_CU * cus
         res["atomics"] = {"ok": bad == 0, "iters": SIM_ATOM_ITERS, "layers": SIM_ATOM_LAYERS, "workgroups": wg,
                           "wgPerXcd": [SIM_ATOM_BLOCKS_PER_CU * n for n in full], "cusTested": cus,

@@ -12,6 +12,7 @@ import json
 import threading
 
 from . import lowp, native_path
+from .probe_checks import CHECKS
 
 _lib = None
 _lock = threading.Lock()
@@ -183,14 +184,9 @@ def _run_opts(hbm_bytes: int, mfma: bool, gemm_n: int, patterns: int, gemm_reps:
         opts["mfmaLowPrecision"] = lowp.dtype_mask(low_precision)
     if host_link_bytes > 0:  # absent when off: the default options stay what they were
         opts["hostLinkBytes"] = host_link_bytes
-    if lds_check:  # absent when off, likewise
-        opts["ldsCheck"] = 1
-    if reg_check:
-        opts["regCheck"] = 1
-    if alu_check:
-        opts["aluCheck"] = 1
-    if atom_check:
-        opts["atomCheck"] = 1
+    for check, on in zip(CHECKS, (lds_check, reg_check, alu_check, atom_check)):
+        if on:  # absent when off, likewise
+            opts[check.option] = 1
     return json.dumps(opts).encode()
 
 

@@ -54,8 +54,8 @@
 
 #include "alu_ref.h"  // index, operand windows, fold; the host's expectation
 #include "arena.h"    // kCuKeys
-#include "census.h"   // cu_key, simd_id
-#include "ctx.h"      // DeviceCtx: the phase's events, counters, expectation table and pinned result
+#include "census.h"   // cu_key, simd_id, decode_dump
+#include "ctx.h"      // DeviceCtx, CounterSets: the phase's events, counters, expectation table and pinned result
 #include "hbm.h"      // pattern_word, umin64
 #include "options.h"  // alu::Plan
 #include "report.h"   // AluResult
@@ -68,7 +68,7 @@ constexpr int kThreads = 256;
 constexpr int kMapWords = kCuKeys * 4 / 64;  // one bit per (CU key, SIMD)
 static_assert(kPlanGroups == kGroups && kPlanLanes == kLanes && kPlanSeedBase == kSeedBase, "options.h mirrors alu_ref.h");
 
-// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (see lds.h). The
+// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (ctx.h CounterSets). The
 // consensus slot (0: empty) and its publisher are part of the set.
 constexpr int kSlotBadWaves = 0, kSlotBadLanes = 1, kSlotFirstBad = 2, kSlotWorkgroups = 3, kSlotWaves = 4 /* 4 of them */,
               kSlotSplit = 8, kSlotFirstSplit = 9, kSlotConsensus = 10, kSlotPublisher = 11, kSlotDumpCu = 12,
@@ -433,50 +433,37 @@ __global__ __launch_bounds__(kThreads) void alu_march(const KernelArgs a) {
 }
 
 // ------------------------------------------------------------------ the phase: ensure / launch / finish
-// Makes the phase's events, counter sets, pinned result and expectation table (and, ``dump_stage``
-// 1 | 2, the device copy of one workgroup's digests, 3, of its trans trace), puts both counter sets
-// at their reset values unless the last run left them so, and computes and uploads the host's
-// expectation when (seed, steps) is not the pair the table holds. All of it ahead of the probe's clock.
-inline void ensure(DeviceCtx& c, const Plan& pl, int dump_stage) {
-  if (!c.alu_res) {  // set last: a failure half way is picked up by the next probe that asks
-    for (auto& e : c.alu_ev)
-      if (!e) PROBE_CHECK(hipEventCreate(&e));
-    if (!c.alu_cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.alu_cnt), 2 * kSlots * sizeof(unsigned long long)));
-    if (!c.alu_exp) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.alu_exp), kExactGroups * kLanes * sizeof(uint32_t)));
-    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.alu_res), kSlots * sizeof(unsigned long long)));
-    c.alu_clean = false;
-    c.alu_exp_iters = 0;
-  }
-  const bool stale = c.alu_exp_iters != pl.iters || c.alu_exp_seed != pl.seed;
-  if (!c.alu_clean || stale) {  // first use, a run that never reached finish(), or a table a run may still read
-    PROBE_CHECK(hipStreamSynchronize(c.stream));
-    PROBE_CHECK(hipStreamSynchronize(c.stream2));
-  }
-  if (!c.alu_clean) {
-    std::vector<unsigned long long> init(2 * kSlots);
-    for (int i = 0; i < 2 * kSlots; ++i) init[i] = reset_value(i % kSlots);
-    PROBE_CHECK(hipMemcpy(c.alu_cnt, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    c.alu_set = 0;
-    c.alu_clean = true;
-  }
+// Makes the phase's expectation table and counter sets (and, for dump stage 1 | 2, the device copy of
+// one workgroup's digests, 3, of its trans trace), puts both sets at their reset values unless the
+// last run left them so, and computes and uploads the host's expectation when (seed, steps) is not
+// the pair the table holds. All of it ahead of the probe's clock.
+inline void ensure(DeviceCtx& c, const Plan& pl) {
+  auto& x = c.alu;
+  if (!x.exp) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&x.exp), kExactGroups * kLanes * sizeof(uint32_t)));
+  x.sets.make(kSlots);
+  const bool stale = x.exp_iters != pl.iters || x.exp_seed != pl.seed;
+  // first use, a run that never reached finish(), or a table a run may still read
+  if (!x.sets.clean || stale) sync_streams(c);
+  if (!x.sets.clean) x.sets.reset<kSlots>(reset_value);
   if (stale) {
     uint32_t table[kExactGroups * kLanes];
     expected(pl.seed, pl.iters, table);
-    c.alu_exp_iters = 0;
-    PROBE_CHECK(hipMemcpy(c.alu_exp, table, sizeof table, hipMemcpyHostToDevice));
-    c.alu_exp_seed = pl.seed;
-    c.alu_exp_iters = pl.iters;
+    x.exp_iters = 0;
+    PROBE_CHECK(hipMemcpy(x.exp, table, sizeof table, hipMemcpyHostToDevice));
+    x.exp_seed = pl.seed;
+    x.exp_iters = pl.iters;
   }
-  if ((dump_stage == 1 || dump_stage == 2) && !c.alu_dump) PROBE_CHECK(hipMalloc(&c.alu_dump, kDumpBytes));
-  if (dump_stage == 3 && !c.alu_trace) PROBE_CHECK(hipMalloc(&c.alu_trace, kTraceBytes));
+  if ((pl.dump_stage == 1 || pl.dump_stage == 2) && !x.dump) PROBE_CHECK(hipMalloc(&x.dump, kDumpBytes));
+  if (pl.dump_stage == 3 && !x.trace) PROBE_CHECK(hipMalloc(&x.trace, kTraceBytes));
 }
 
 // Enqueues the phase on stream s: an event, the kernel, an event, the counters' copy. No host synchronise.
 inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
+  auto& x = c.alu;
   KernelArgs a{};
   a.seed = pl.seed;
   a.iters = pl.iters;
-  a.expect = c.alu_exp;
+  a.expect = x.exp;
   a.flip_group = pl.flip_group;
   a.flip_step = pl.flip_group >= 0 ? static_cast<uint32_t>(pl.flip_step) : ~0u;
   a.flip_lane = pl.flip_group >= 0 ? static_cast<uint32_t>(pl.flip_lane) : ~0u;
@@ -484,28 +471,24 @@ inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
   a.fault_simd = pl.fault_simd;
   a.fault_xcc = pl.fault_xcc;
   // a stage without its buffer (a probe, which has no caller buffer) is off
-  a.dump_stage = (pl.dump_stage == 3 ? c.alu_trace : c.alu_dump) ? pl.dump_stage : 0;
-  a.dump = static_cast<uint32_t*>(c.alu_dump);
-  a.trace = static_cast<uint32_t*>(c.alu_trace);
-  a.cnt = c.alu_cnt + c.alu_set * kSlots;
-  a.next = c.alu_cnt + (c.alu_set ^ 1) * kSlots;
+  a.dump_stage = (pl.dump_stage == 3 ? x.trace : x.dump) ? pl.dump_stage : 0;
+  a.dump = static_cast<uint32_t*>(x.dump);
+  a.trace = static_cast<uint32_t*>(x.trace);
   const int grid = pl.blocks_per_cu * c.prop.multiProcessorCount;
-  c.alu_clean = false;  // until finish() has seen this run end
   // the trace holds the first min(iters, kTraceSteps) steps; what the run does not write reads as zero
-  if (a.dump_stage == 3) PROBE_CHECK(hipMemsetAsync(c.alu_trace, 0, kTraceBytes, s));
-  PROBE_CHECK(hipEventRecord(c.alu_ev[0], s));
-  if (pl.test_kernel()) hipLaunchKernelGGL(alu_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL(alu_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
-  PROBE_CHECK(hipEventRecord(c.alu_ev[1], s));
-  PROBE_CHECK(hipGetLastError());
-  PROBE_CHECK(hipMemcpyAsync(c.alu_res, a.cnt, kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  if (a.dump_stage == 3) PROBE_CHECK(hipMemsetAsync(x.trace, 0, kTraceBytes, s));
+  x.sets.run(s, kSlots, [&](unsigned long long* cnt, unsigned long long* next) {
+    a.cnt = cnt;
+    a.next = next;
+    if (pl.test_kernel()) hipLaunchKernelGGL(alu_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL(alu_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
+  });
 }
 
-// After the stream's synchronise: the counters -> the "alu" block's result; the next run takes the
-// other counter set, which this run's kernel reset.
+// After the stream's synchronise: the counters -> the "alu" block's result.
 inline AluResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   AluResult r;
-  const unsigned long long* h = c.alu_res;
+  const unsigned long long* h = c.alu.sets.res;
   r.iters = pl.iters;
   r.expected = c.prop.multiProcessorCount;
   r.require_all = require_all;
@@ -520,10 +503,7 @@ inline AluResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
     const unsigned long long who = 2 * r.split_waves > r.waves() ? h[kSlotPublisher] : h[kSlotFirstSplit];
     r.suspect = who == ~0ull ? -1 : static_cast<long long>(who);
   }
-  if (pl.dump_stage && h[kSlotDumpCu] != ~0ull) {
-    r.dump_cu = static_cast<int>(h[kSlotDumpCu]);
-    for (int w = 0; w < 4; ++w) r.dump_simds[w] = static_cast<int>((h[kSlotDumpSimds] >> (8 * w)) & 0xFF);
-  }
+  if (pl.dump_stage) decode_dump(h[kSlotDumpCu], h[kSlotDumpSimds], &r.dump_cu, r.dump_simds);
   for (int w = 0; w < kMapWords; ++w) {
     const unsigned long long ok = h[kSlotOkMap + w], bad = h[kSlotBadMap + w], ver = ok & ~bad;
     r.simds_tested += __builtin_popcountll(ok | bad);
@@ -534,9 +514,7 @@ inline AluResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
       if ((bad >> (4 * cu)) & 15ull) ++r.bad_cus;
     }
   }
-  PROBE_CHECK(hipEventElapsedTime(&r.ms, c.alu_ev[0], c.alu_ev[1]));
-  c.alu_set ^= 1;
-  c.alu_clean = true;
+  r.ms = c.alu.sets.end();
   return r;
 }
 

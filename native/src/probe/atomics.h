@@ -53,7 +53,7 @@
 
 #include "arena.h"        // kCuKeys, kCuMapWords
 #include "atomics_ref.h"  // layout, operands, host expectation
-#include "census.h"       // cu_key, simd_id
+#include "census.h"       // cu_key, simd_id, fold_cus, decode_dump
 #include "ctx.h"
 #include "hbm.h"      // umin64
 #include "options.h"  // atom::Plan
@@ -74,7 +74,7 @@ constexpr int kLds16Off = kRegionWords + 16;
 constexpr int kTicketWord = kRegionWords, kTicketMap = kRegionWords + 1;
 constexpr int kBadWgWords = kMaxWorkgroups / 64;
 
-// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (see lds.h).
+// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (ctx.h CounterSets).
 constexpr int kSlotLdsBad = 0, kSlotL2Bad = 1, kSlotDevBad = 2, kSlotBadReturns = 3, kSlotTicket = 4, kSlotFirstBad = 5,
               kSlotWorkgroups = 6, kSlotDumpCu = 7, kSlotDumpSimds = 8, kSlotWgXcd = 9 /* 8 of them */,
               kSlotTested = 17, kSlotBadCu = kSlotTested + kCuMapWords, kSlotBadWg = kSlotBadCu + kCuMapWords,
@@ -476,77 +476,67 @@ __global__ __launch_bounds__(kThreads) void atom_verify(const VerifyArgs a) {
 // ------------------------------------------------------------------ the phase: ensure / launch / finish
 // the grid of a plan: never more workgroups than the bad-workgroup map and the dump's records hold
 inline int grid_of(const DeviceCtx& c, const Plan& pl) { return std::min(kMaxWorkgroups, pl.blocks_per_cu * c.prop.multiProcessorCount); }
-inline uint32_t* regions_of(DeviceCtx& c) { return c.atom_mem; }
-inline uint32_t* dev_of(DeviceCtx& c) { return c.atom_mem + static_cast<size_t>(c.atom_wgs) * kRegionWords; }
+inline uint32_t* regions_of(DeviceCtx& c) { return c.atom.mem; }
+inline uint32_t* dev_of(DeviceCtx& c) { return c.atom.mem + static_cast<size_t>(c.atom.wgs) * kRegionWords; }
 inline uint2* records_of(DeviceCtx& c) { return reinterpret_cast<uint2*>(dev_of(c) + kDevRowSets * kRowSetWords); }
 
-// Makes the phase's events, counter sets, pinned result, expectation table and data buffers (and,
-// ``want_dump``, the device copy of the dump); grows the data buffers when the plan's grid is larger
-// than the one they were made for and runs atom_verify in init-only mode on new ones; puts both
-// counter sets at their reset values unless the last run left them so; computes and uploads the
-// host's expectation when (seed, iters) is not the pair the table holds. All ahead of the probe's clock.
-inline void ensure(DeviceCtx& c, const Plan& pl, bool want_dump) {
-  if (!c.atom_res) {  // set last: a failure half way is picked up by the next probe that asks
-    for (auto& e : c.atom_ev)
-      if (!e) PROBE_CHECK(hipEventCreate(&e));
-    if (!c.atom_cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.atom_cnt), 2 * kSlots * sizeof(unsigned long long)));
-    if (!c.atom_exp) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.atom_exp), kExpWords * sizeof(uint32_t)));
-    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.atom_res), kSlots * sizeof(unsigned long long)));
-    c.atom_clean = false;
-    c.atom_exp_iters = 0;
-  }
+// Makes the phase's expectation table, counter sets and data buffers (and, for a dump stage, the
+// device copy of the dump); grows the data buffers when the plan's grid is larger than the one they
+// were made for and runs atom_verify in init-only mode on new ones; puts both counter sets at their
+// reset values unless the last run left them so; computes and uploads the host's expectation when
+// (seed, iters) is not the pair the table holds. All ahead of the probe's clock.
+inline void ensure(DeviceCtx& c, const Plan& pl) {
+  auto& x = c.atom;
+  if (!x.ev_mid) PROBE_CHECK(hipEventCreate(&x.ev_mid));
+  if (!x.exp) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&x.exp), kExpWords * sizeof(uint32_t)));
+  x.sets.make(kSlots);
   const int grid = grid_of(c, pl);
-  const bool stale = c.atom_exp_iters != pl.iters || c.atom_exp_seed != pl.seed;
-  const bool grow = grid > c.atom_wgs;
-  if (!c.atom_clean || stale || grow) {  // first use, a run that never reached finish(), or buffers a run may still use
-    PROBE_CHECK(hipStreamSynchronize(c.stream));
-    PROBE_CHECK(hipStreamSynchronize(c.stream2));
-  }
+  const bool stale = x.exp_iters != pl.iters || x.exp_seed != pl.seed;
+  const bool grow = grid > x.wgs;
+  // first use, a run that never reached finish(), or buffers a run may still use
+  if (!x.sets.clean || stale || grow) sync_streams(c);
   if (grow) {
-    if (c.atom_mem) PROBE_CHECK(hipFree(c.atom_mem));
-    c.atom_mem = nullptr;
-    c.atom_wgs = 0;
+    if (x.mem) PROBE_CHECK(hipFree(x.mem));
+    x.mem = nullptr;
+    x.wgs = 0;
     const size_t words = static_cast<size_t>(grid) * kRegionWords + kDevRowSets * kRowSetWords + static_cast<size_t>(grid) * 2;
-    PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.atom_mem), words * sizeof(uint32_t)));
-    c.atom_wgs = grid;
-    c.atom_clean = false;  // a run cut short may have left any word behind: the whole buffer is initialised below
+    PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&x.mem), words * sizeof(uint32_t)));
+    x.wgs = grid;
+    x.sets.clean = false;  // a run cut short may have left any word behind: the whole buffer is initialised below
   }
-  if (!c.atom_clean) {
-    std::vector<unsigned long long> init(2 * kSlots);
-    for (int i = 0; i < 2 * kSlots; ++i) init[i] = reset_value(i % kSlots);
-    PROBE_CHECK(hipMemcpy(c.atom_cnt, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    VerifyArgs v{};
-    v.nwg = c.atom_wgs;
-    v.init_only = 1;
-    v.regions = regions_of(c);
-    v.dev = dev_of(c);
-    v.records = records_of(c);
-    v.cnt = c.atom_cnt;
-    hipLaunchKernelGGL(atom_verify, dim3(c.atom_wgs + kDevRowSets * kOps), dim3(kThreads), 0, c.stream, v);
-    PROBE_CHECK(hipGetLastError());
-    PROBE_CHECK(hipStreamSynchronize(c.stream));
-    c.atom_set = 0;
-    c.atom_clean = true;
-  }
+  if (!x.sets.clean)
+    x.sets.reset<kSlots>(reset_value, [&] {
+      VerifyArgs v{};
+      v.nwg = x.wgs;
+      v.init_only = 1;
+      v.regions = regions_of(c);
+      v.dev = dev_of(c);
+      v.records = records_of(c);
+      v.cnt = x.sets.cnt;
+      hipLaunchKernelGGL(atom_verify, dim3(x.wgs + kDevRowSets * kOps), dim3(kThreads), 0, c.stream, v);
+      PROBE_CHECK(hipGetLastError());
+      PROBE_CHECK(hipStreamSynchronize(c.stream));
+    });
   if (stale) {
     std::vector<uint32_t> table(kExpWords);
     expected(pl.seed, pl.iters, table.data());
-    c.atom_exp_iters = 0;
-    PROBE_CHECK(hipMemcpy(c.atom_exp, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c.atom_exp_seed = pl.seed;
-    c.atom_exp_iters = pl.iters;
+    x.exp_iters = 0;
+    PROBE_CHECK(hipMemcpy(x.exp, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    x.exp_seed = pl.seed;
+    x.exp_iters = pl.iters;
   }
-  if (want_dump && !c.atom_dump) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.atom_dump), kDumpBytes));
+  if (pl.dump_stage && !x.dump) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&x.dump), kDumpBytes));
 }
 
 // Enqueues the phase on stream s: an event, the two kernels, an event, the counters' copy. No host synchronise.
 inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
-  const int grid = grid_of(c, pl);  // <= c.atom_wgs by ensure()
+  auto& x = c.atom;
+  const int grid = grid_of(c, pl);  // <= x.wgs by ensure()
   KernelArgs a{};
   a.seed = pl.seed;
   a.iters = pl.iters;
   a.layers = pl.layers;
-  a.expect = c.atom_exp;
+  a.expect = x.exp;
   a.regions = regions_of(c);
   a.dev = dev_of(c);
   a.records = records_of(c);
@@ -555,38 +545,34 @@ inline void launch(DeviceCtx& c, hipStream_t s, const Plan& pl) {
   a.flip_bit = pl.flip_bit;
   a.fault_xcc = pl.fault_xcc;
   a.fault_wg = pl.fault_wg;
-  a.dump_stage = c.atom_dump ? pl.dump_stage : 0;
-  a.dump = a.dump_stage ? c.atom_dump : nullptr;
-  a.cnt = c.atom_cnt + c.atom_set * kSlots;
-  a.next = c.atom_cnt + (c.atom_set ^ 1) * kSlots;
+  a.dump_stage = x.dump ? pl.dump_stage : 0;
+  a.dump = a.dump_stage ? x.dump : nullptr;
   VerifyArgs v{};
   v.seed = pl.seed;
   v.nwg = grid;
   v.layers = pl.layers;
-  v.expect = c.atom_exp;
+  v.expect = x.exp;
   v.regions = a.regions;
   v.dev = a.dev;
   v.records = a.records;
   v.dump = a.dump;
-  v.cnt = a.cnt;
-  c.atom_clean = false;  // until finish() has seen this run end
   // a dump run starts from a zeroed buffer: what a layer that does not run would have written reads 0
-  if (a.dump) PROBE_CHECK(hipMemsetAsync(c.atom_dump, 0, kDumpBytes, s));
-  PROBE_CHECK(hipEventRecord(c.atom_ev[0], s));
-  if (pl.test_kernel()) hipLaunchKernelGGL(atom_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL(atom_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
-  if (pl.time_kernels) PROBE_CHECK(hipEventRecord(c.atom_ev[2], s));
-  hipLaunchKernelGGL(atom_verify, dim3(grid + kDevRowSets * kOps), dim3(kThreads), 0, s, v);
-  PROBE_CHECK(hipEventRecord(c.atom_ev[1], s));
-  PROBE_CHECK(hipGetLastError());
-  PROBE_CHECK(hipMemcpyAsync(c.atom_res, a.cnt, kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  if (a.dump) PROBE_CHECK(hipMemsetAsync(x.dump, 0, kDumpBytes, s));
+  x.sets.run(s, kSlots, [&](unsigned long long* cnt, unsigned long long* next) {
+    a.cnt = v.cnt = cnt;
+    a.next = next;
+    if (pl.test_kernel()) hipLaunchKernelGGL(atom_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL(atom_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
+    if (pl.time_kernels) PROBE_CHECK(hipEventRecord(x.ev_mid, s));
+    hipLaunchKernelGGL(atom_verify, dim3(grid + kDevRowSets * kOps), dim3(kThreads), 0, s, v);
+  });
 }
 
-// After the stream's synchronise: the counters -> the "atomics" block's result; the next run takes
-// the other counter set, which this run's kernel reset.
+// After the stream's synchronise: the counters -> the "atomics" block's result.
 inline AtomResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   AtomResult r;
-  const unsigned long long* h = c.atom_res;
+  CounterSets& cs = c.atom.sets;
+  const unsigned long long* h = cs.res;
   r.iters = pl.iters;
   r.layers = pl.layers;
   r.expected = c.prop.multiProcessorCount;
@@ -599,25 +585,21 @@ inline AtomResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   r.bad_returns = h[kSlotBadReturns];
   r.ticket_faults = h[kSlotTicket];
   r.first_bad = h[kSlotFirstBad];
-  if (pl.dump_stage && h[kSlotDumpCu] != ~0ull) {
-    r.dump_cu = static_cast<int>(h[kSlotDumpCu]);
-    for (int w = 0; w < 4; ++w) r.dump_simds[w] = static_cast<int>((h[kSlotDumpSimds] >> (8 * w)) & 0xFF);
-  }
-  for (int w = 0; w < kCuMapWords; ++w) {
-    const unsigned long long tested = h[kSlotTested + w], bad = h[kSlotBadCu + w], ver = tested & ~bad;
-    r.cus_tested += __builtin_popcountll(tested | bad);
-    r.cus_verified += __builtin_popcountll(ver);
-    r.bad_cus += __builtin_popcountll(bad);
-    r.per_xcd[(w * 64) >> 8] += __builtin_popcountll(ver);  // 256 CU keys per XCD
-  }
+  if (pl.dump_stage) decode_dump(h[kSlotDumpCu], h[kSlotDumpSimds], &r.dump_cu, r.dump_simds);
+  // a CU in the bad map counts as tested, whether or not a clean workgroup ran there too
+  unsigned long long tested[kCuMapWords];
+  for (int w = 0; w < kCuMapWords; ++w) tested[w] = h[kSlotTested + w] | h[kSlotBadCu + w];
+  const CuFold f = fold_cus(tested, h + kSlotBadCu);
+  r.cus_tested = f.tested;
+  r.cus_verified = f.verified;
+  r.bad_cus = f.bad;
+  for (int x = 0; x < 8; ++x) r.per_xcd[x] = f.per_xcd[x];
   for (int w = 0; w < kBadWgWords; ++w) r.bad_workgroups += __builtin_popcountll(h[kSlotBadWg + w]);
-  PROBE_CHECK(hipEventElapsedTime(&r.ms, c.atom_ev[0], c.atom_ev[1]));
   if (pl.time_kernels) {
-    PROBE_CHECK(hipEventElapsedTime(&r.march_ms, c.atom_ev[0], c.atom_ev[2]));
-    PROBE_CHECK(hipEventElapsedTime(&r.verify_ms, c.atom_ev[2], c.atom_ev[1]));
+    PROBE_CHECK(hipEventElapsedTime(&r.march_ms, cs.ev[0], c.atom.ev_mid));
+    PROBE_CHECK(hipEventElapsedTime(&r.verify_ms, c.atom.ev_mid, cs.ev[1]));
   }
-  c.atom_set ^= 1;
-  c.atom_clean = true;
+  r.ms = cs.end();
   return r;
 }
 

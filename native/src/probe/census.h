@@ -88,4 +88,31 @@ inline CuCount count_cus(const unsigned long long* map) {
   return c;
 }
 
+// The two CU maps of a per-CU phase (lds.h, regfile.h, atomics.h) folded: CUs tested, CUs with a
+// fault, and the tested ones without, in all and per XCD.
+struct CuFold {
+  int tested = 0, bad = 0, verified = 0;
+  int per_xcd[8] = {};  // verified
+};
+
+inline CuFold fold_cus(const unsigned long long* tested, const unsigned long long* bad) {
+  unsigned long long verified[kCuMapWords];
+  for (int w = 0; w < kCuMapWords; ++w) verified[w] = tested[w] & ~bad[w];
+  CuFold f;
+  f.tested = count_cus(tested).total;
+  f.bad = count_cus(bad).total;
+  const CuCount v = count_cus(verified);
+  f.verified = v.total;
+  for (int x = 0; x < 8; ++x) f.per_xcd[x] = v.per_xcc[x];
+  return f;
+}
+
+// A dump run's kSlotDumpCu / kSlotDumpSimds (all-ones: no workgroup 0 reported) -> the CU key of the
+// dumped workgroup and the SIMD each of its four waves ran on.
+inline void decode_dump(unsigned long long cu, unsigned long long simds, int* dump_cu, int* dump_simds) {
+  if (cu == ~0ull) return;
+  *dump_cu = static_cast<int>(cu);
+  for (int w = 0; w < 4; ++w) dump_simds[w] = static_cast<int>((simds >> (8 * w)) & 0xFF);
+}
+
 }  // namespace

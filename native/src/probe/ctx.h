@@ -23,6 +23,74 @@ struct SweepBuf {
   bool empty() const { return chunks.empty(); }
 };
 
+// The counters of one opt-in per-CU phase (lds.h, regfile.h, alu.h, atomics.h): two sets on the
+// device, a pinned copy of the set a run used, and the two events around the run's kernels.
+//
+// The kernel of a run counts into one set with atomics and its workgroup 0 resets the OTHER set for
+// the next run with plain stores: a reset of the set in use would race with the atomics of
+// workgroups on other XCDs (their L2s are not coherent inside one kernel), and the end of the kernel
+// is what makes the plain stores visible to the next run's atomics. So run() hands the kernel
+// ``set`` to count into and ``set ^ 1`` to reset, end() flips ``set``, and ``clean`` says that both
+// sets hold their reset values: false from run() until end() has seen the run finish, so a run that
+// threw before end() is recovered from by the next reset().
+struct CounterSets {
+  hipEvent_t ev[2] = {};
+  unsigned long long* cnt = nullptr;  // device, 2 sets
+  unsigned long long* res = nullptr;  // pinned copy of the set a run used
+  int set = 0;
+  bool clean = false;  // both sets hold their reset values
+
+  // The events, the two sets of ``slots`` counters and the pinned copy, on first use.
+  void make(int slots) {
+    if (res) return;  // set last: a failure half way is picked up by the next probe that asks
+    for (auto& e : ev)
+      if (!e) PROBE_CHECK(hipEventCreate(&e));
+    if (!cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&cnt), 2 * slots * sizeof(unsigned long long)));
+    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&res), slots * sizeof(unsigned long long)));
+    clean = false;
+  }
+
+  // Both sets to the phase's reset_value(slot), set 0 the next to count into. For sets that are not
+  // clean (first use, or a run that never reached end()); the caller has synchronised every stream
+  // a run may be on. ``also``: what else the phase puts right before the sets count as clean.
+  template <int kSlots, class Reset, class Also>
+  void reset(Reset reset_value, Also&& also) {
+    unsigned long long init[2 * kSlots];
+    for (int i = 0; i < 2 * kSlots; ++i) init[i] = reset_value(i % kSlots);
+    PROBE_CHECK(hipMemcpy(cnt, init, sizeof init, hipMemcpyHostToDevice));
+    also();
+    set = 0;
+    clean = true;
+  }
+  template <int kSlots, class Reset>
+  void reset(Reset reset_value) {
+    reset<kSlots>(reset_value, [] {});
+  }
+
+  // Enqueues a run on stream s: an event, ``kernels(cnt, next)`` (the set to count into and the one
+  // to reset), an event, the copy of the run's set to ``res``. No host synchronise.
+  template <class Kernels>
+  void run(hipStream_t s, int slots, Kernels&& kernels) {
+    unsigned long long* mine = cnt + set * slots;
+    clean = false;  // until end() has seen this run end
+    PROBE_CHECK(hipEventRecord(ev[0], s));
+    kernels(mine, cnt + (set ^ 1) * slots);
+    PROBE_CHECK(hipEventRecord(ev[1], s));
+    PROBE_CHECK(hipGetLastError());
+    PROBE_CHECK(hipMemcpyAsync(res, mine, slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  }
+
+  // After the stream's synchronise: the run's time between the events; the next run takes the other
+  // set, which this run's kernel reset.
+  float end() {
+    float ms = 0;
+    PROBE_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    set ^= 1;
+    clean = true;
+    return ms;
+  }
+};
+
 struct DeviceCtx {
   hipStream_t stream = nullptr;   // HBM pattern test
   hipStream_t stream2 = nullptr;  // MFMA checks, overlapped with the bandwidth-bound HBM test
@@ -45,54 +113,45 @@ struct DeviceCtx {
   bool hl_coherent = true;
   unsigned long long* hl_cnt = nullptr;  // device counter pairs, one per pass
   unsigned long long* hl_res = nullptr;  // their pinned copy
-  // LDS phase ("ldsCheck"): created by the first probe that asks. Two sets of device counters: the
-  // kernel of one run counts into set lds_set and resets the other for the next run (lds.h).
-  hipEvent_t lds_ev[2] = {};
-  unsigned long long* lds_cnt = nullptr;  // device, 2 sets
-  unsigned long long* lds_res = nullptr;  // pinned copy of the set a run used
-  int lds_set = 0;
-  bool lds_clean = false;    // both sets hold their reset values
-  uint32_t lds_runs = 0;     // the default "ldsSalt"
-  void* lds_dump = nullptr;  // device copy of workgroup 0's LDS (mi355x_probe_lds with an image)
-  // register-file phase ("regCheck"): as the LDS phase's. regs_attr[i] is what the runtime says of
-  // rf_march<i>: registers per lane and workgroups per CU, asked once (0: not yet).
-  hipEvent_t regs_ev[2] = {};
-  unsigned long long* regs_cnt = nullptr;  // device, 2 sets
-  unsigned long long* regs_res = nullptr;  // pinned copy of the set a run used
-  int regs_set = 0;
-  bool regs_clean = false;
-  uint32_t regs_runs = 0;     // the default "regsSalt"
-  void* regs_dump = nullptr;  // device image uint32[4][512][64] (mi355x_probe_regs with an image)
-  int regs_attr[2][2] = {};
-  // vector-ALU phase ("aluCheck"): events, counter sets and pinned result as the LDS phase's.
-  // alu_exp holds the host's expectation uint32[5][64] of (alu_exp_seed, alu_exp_iters), computed
-  // and uploaded once per context and pair; alu_exp1 the one of the dump's stage 1 (one step).
-  hipEvent_t alu_ev[2] = {};
-  unsigned long long* alu_cnt = nullptr;  // device, 2 sets
-  unsigned long long* alu_res = nullptr;  // pinned copy of the set a run used
-  int alu_set = 0;
-  bool alu_clean = false;
-  uint32_t* alu_exp = nullptr;  // device
-  uint32_t alu_exp_seed = 0;
-  int alu_exp_iters = 0;        // 0: nothing uploaded yet
-  void* alu_dump = nullptr;     // device uint32[4][6][64] (mi355x_probe_alu with a dump buffer)
-  void* alu_trace = nullptr;    // device uint32[4][64][12][64] (... with "aluDumpStage":3: the trans trace)
-  // atomic-unit phase ("atomCheck"): events, counter sets and pinned result as the LDS phase's.
-  // atom_mem is one allocation for atom_wgs workgroups: their private regions, the nine dev
-  // row-sets and the records; made by the first probe that asks, grown for a larger grid, never
-  // shrunk. atom_verify leaves every word at its op's identity, so a run needs no memset.
-  // atom_exp holds the host's expectation (atomics_ref.h kExpWords) of (atom_exp_seed, atom_exp_iters).
-  hipEvent_t atom_ev[3] = {};  // [2]: between the two kernels, recorded only for "atomTimeKernels"
-  unsigned long long* atom_cnt = nullptr;  // device, 2 sets
-  unsigned long long* atom_res = nullptr;  // pinned copy of the set a run used
-  int atom_set = 0;
-  bool atom_clean = false;
-  uint32_t* atom_mem = nullptr;  // device
-  int atom_wgs = 0;              // the grid atom_mem was sized for
-  uint32_t* atom_exp = nullptr;  // device
-  uint32_t atom_exp_seed = 0;
-  int atom_exp_iters = 0;        // 0: nothing uploaded yet
-  uint32_t* atom_dump = nullptr;  // device uint32[kDumpWords] (mi355x_probe_atomics with a dump buffer)
+  // The opt-in per-CU phases, each made by the first probe that asks: its counter sets (above) and
+  // what else it keeps between runs.
+  struct {  // "ldsCheck" (lds.h)
+    CounterSets sets;
+    uint32_t runs = 0;     // the default "ldsSalt"
+    void* dump = nullptr;  // device copy of workgroup 0's LDS (mi355x_probe_lds with an image)
+  } lds;
+  // regs.attr[i] is what the runtime says of rf_march<i>: registers per lane and workgroups per CU,
+  // asked once (0: not yet).
+  struct {  // "regCheck" (regfile.h)
+    CounterSets sets;
+    uint32_t runs = 0;     // the default "regsSalt"
+    void* dump = nullptr;  // device image uint32[4][512][64] (mi355x_probe_regs with an image)
+    int attr[2][2] = {};
+  } regs;
+  // alu.exp holds the host's expectation uint32[5][64] of (exp_seed, exp_iters), computed and
+  // uploaded once per context and pair.
+  struct {  // "aluCheck" (alu.h)
+    CounterSets sets;
+    uint32_t* exp = nullptr;  // device
+    uint32_t exp_seed = 0;
+    int exp_iters = 0;        // 0: nothing uploaded yet
+    void* dump = nullptr;     // device uint32[4][6][64] (mi355x_probe_alu with a dump buffer)
+    void* trace = nullptr;    // device uint32[4][64][12][64] (... with "aluDumpStage":3: the trans trace)
+  } alu;
+  // atom.mem is one allocation for atom.wgs workgroups: their private regions, the nine dev row-sets
+  // and the records; made by the first probe that asks, grown for a larger grid, never shrunk.
+  // atom_verify leaves every word at its op's identity, so a run needs no memset. atom.exp holds
+  // the host's expectation (atomics_ref.h kExpWords) of (exp_seed, exp_iters).
+  struct {  // "atomCheck" (atomics.h)
+    CounterSets sets;
+    hipEvent_t ev_mid = nullptr;  // between the two kernels, recorded only for "atomTimeKernels"
+    uint32_t* mem = nullptr;      // device
+    int wgs = 0;                  // the grid mem was sized for
+    uint32_t* exp = nullptr;      // device
+    uint32_t exp_seed = 0;
+    int exp_iters = 0;            // 0: nothing uploaded yet
+    uint32_t* dump = nullptr;     // device uint32[kDumpWords] (mi355x_probe_atomics with a dump buffer)
+  } atom;
   // The probe arena is kept between probes (a hipMalloc of ~1.2 GiB costs ~0.25 ms, a fifth of a
   // probe) and freed by mi355x_probe_trim once idle, so a pod on the GPU gets the memory back.
   void* arena = nullptr;
@@ -131,6 +190,12 @@ inline std::mutex& device_mutex(int dev) {
 
 inline DeviceCtx& ctx_of(int dev) { return g_ctx[static_cast<size_t>(dev)]; }
 inline bool device_ok(int dev) { return g_count >= 0 && dev >= 0 && dev < g_count; }
+
+// What a phase does before it resets its counter sets or replaces a buffer a run may still use.
+inline void sync_streams(DeviceCtx& c) {
+  PROBE_CHECK(hipStreamSynchronize(c.stream));
+  PROBE_CHECK(hipStreamSynchronize(c.stream2));
+}
 
 inline double ms_since(std::chrono::steady_clock::time_point a) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();

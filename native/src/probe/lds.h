@@ -20,8 +20,8 @@
 #include <cstdint>
 
 #include "arena.h"    // kCuMapWords
-#include "census.h"   // cu_key, count_cus
-#include "ctx.h"      // DeviceCtx: the phase's events, counters and pinned result
+#include "census.h"   // cu_key, fold_cus
+#include "ctx.h"      // DeviceCtx, CounterSets: the phase's events, counters and pinned result
 #include "hbm.h"      // pattern16, mismatches16, umin64
 #include "options.h"  // lds::Plan, lds::kBytesPerCU
 #include "report.h"   // LdsResult
@@ -33,10 +33,7 @@ namespace lds {
 constexpr int kThreads = 256;
 constexpr uint32_t kChunksPerCU = kBytesPerCU / 16;
 
-// One set of counters. The kernel of a run counts into one set with atomics and its workgroup 0
-// resets the OTHER set for the next run with plain stores: a reset of the set in use would race
-// with the atomics of workgroups on other XCDs (their L2s are not coherent inside one kernel), and
-// the end of the kernel is what makes the plain stores visible to the next run's atomics.
+// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (ctx.h CounterSets).
 constexpr int kSlotBadBits = 0, kSlotFirstBad = 1, kSlotWorkgroups = 2, kSlotDumpCu = 3, kSlotTested = 4,
               kSlotBad = kSlotTested + kCuMapWords, kSlots = kSlotBad + kCuMapWords;
 static_assert(kSlots <= kThreads, "workgroup 0 resets a counter set with one store per thread");
@@ -168,33 +165,23 @@ __global__ __launch_bounds__(kThreads) void lds_march(const KernelArgs a) {
 }
 
 // ------------------------------------------------------------------ the phase: ensure / launch / finish
-// Makes the phase's events, counter sets and pinned result (and, ``want_dump``, the device image of
-// one LDS), and puts both counter sets at their reset values unless the last run left them so.
-inline void ensure(DeviceCtx& c, bool want_dump) {
-  if (!c.lds_res) {  // set last: a failure half way is picked up by the next probe that asks
-    for (auto& e : c.lds_ev)
-      if (!e) PROBE_CHECK(hipEventCreate(&e));
-    if (!c.lds_cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.lds_cnt), 2 * kSlots * sizeof(unsigned long long)));
-    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.lds_res), kSlots * sizeof(unsigned long long)));
-    c.lds_clean = false;
+// Makes the phase's counter sets (and, for a dump stage, the device image of one LDS), and puts both
+// sets at their reset values unless the last run left them so.
+inline void ensure(DeviceCtx& c, const Plan& pl) {
+  CounterSets& cs = c.lds.sets;
+  cs.make(kSlots);
+  if (!cs.clean) {  // first use, or a run that never reached finish()
+    sync_streams(c);
+    cs.reset<kSlots>(reset_value);
   }
-  if (!c.lds_clean) {  // first use, or a run that never reached finish()
-    PROBE_CHECK(hipStreamSynchronize(c.stream));
-    PROBE_CHECK(hipStreamSynchronize(c.stream2));
-    unsigned long long init[2 * kSlots];
-    for (int i = 0; i < 2 * kSlots; ++i) init[i] = reset_value(i % kSlots);
-    PROBE_CHECK(hipMemcpy(c.lds_cnt, init, sizeof init, hipMemcpyHostToDevice));
-    c.lds_set = 0;
-    c.lds_clean = true;
-  }
-  if (want_dump && !c.lds_dump) PROBE_CHECK(hipMalloc(&c.lds_dump, kBytesPerCU));
+  if (pl.dump_stage && !c.lds.dump) PROBE_CHECK(hipMalloc(&c.lds.dump, kBytesPerCU));
 }
 
 // Enqueues the phase on stream s: an event, the kernel, an event, the counters' copy. Settles the
 // plan's salt (the context's run counter unless the caller gave one). No host synchronise.
 inline void launch(DeviceCtx& c, hipStream_t s, Plan& pl) {
-  if (!pl.salt_given) pl.salt = c.lds_runs;
-  ++c.lds_runs;
+  if (!pl.salt_given) pl.salt = c.lds.runs;
+  ++c.lds.runs;
   KernelArgs a{};
   a.n16 = pl.n16;
   a.seed = pl.seed ^ pl.salt;
@@ -203,24 +190,20 @@ inline void launch(DeviceCtx& c, hipStream_t s, Plan& pl) {
   a.flip_byte = pl.flip_byte >= 0 && pl.flip_byte < static_cast<long long>(pl.n16) * 16 ? static_cast<uint32_t>(pl.flip_byte) : ~0u;
   a.skip_chunk = pl.skip_chunk >= 0 && pl.skip_chunk < static_cast<long long>(pl.n16) ? static_cast<uint32_t>(pl.skip_chunk) : ~0u;
   a.fault_xcc = pl.fault_xcc;
-  a.dump_stage = c.lds_dump ? pl.dump_stage : 0;
-  a.dump = static_cast<u32x4*>(c.lds_dump);
-  a.cnt = c.lds_cnt + c.lds_set * kSlots;
-  a.next = c.lds_cnt + (c.lds_set ^ 1) * kSlots;
+  a.dump_stage = c.lds.dump ? pl.dump_stage : 0;
+  a.dump = static_cast<u32x4*>(c.lds.dump);
   const int grid = pl.blocks_per_cu * c.prop.multiProcessorCount;
-  c.lds_clean = false;  // until finish() has seen this run end
-  PROBE_CHECK(hipEventRecord(c.lds_ev[0], s));
-  hipLaunchKernelGGL(lds_march, dim3(grid), dim3(kThreads), 0, s, a);
-  PROBE_CHECK(hipEventRecord(c.lds_ev[1], s));
-  PROBE_CHECK(hipGetLastError());
-  PROBE_CHECK(hipMemcpyAsync(c.lds_res, a.cnt, kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  c.lds.sets.run(s, kSlots, [&](unsigned long long* cnt, unsigned long long* next) {
+    a.cnt = cnt;
+    a.next = next;
+    hipLaunchKernelGGL(lds_march, dim3(grid), dim3(kThreads), 0, s, a);
+  });
 }
 
-// After the stream's synchronise: the counters -> the "lds" block's result; the next run takes the
-// other counter set, which this run's kernel reset.
+// After the stream's synchronise: the counters -> the "lds" block's result.
 inline LdsResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   LdsResult r;
-  const unsigned long long* h = c.lds_res;
+  const unsigned long long* h = c.lds.sets.res;
   r.bytes_per_cu = static_cast<uint64_t>(pl.n16) * 16;
   r.patterns = pl.patterns;
   r.salt = pl.salt;
@@ -230,16 +213,12 @@ inline LdsResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   r.bad_bits = h[kSlotBadBits];
   r.first_bad = h[kSlotFirstBad];
   if (pl.dump_stage && h[kSlotDumpCu] != ~0ull) r.dump_cu = static_cast<int>(h[kSlotDumpCu]);
-  unsigned long long verified[kCuMapWords];
-  for (int w = 0; w < kCuMapWords; ++w) verified[w] = h[kSlotTested + w] & ~h[kSlotBad + w];
-  r.tested = count_cus(h + kSlotTested).total;
-  r.bad_cus = count_cus(h + kSlotBad).total;
-  const CuCount v = count_cus(verified);
-  r.verified = v.total;
-  for (int x = 0; x < 8; ++x) r.per_xcd[x] = v.per_xcc[x];
-  PROBE_CHECK(hipEventElapsedTime(&r.ms, c.lds_ev[0], c.lds_ev[1]));
-  c.lds_set ^= 1;
-  c.lds_clean = true;
+  const CuFold f = fold_cus(h + kSlotTested, h + kSlotBad);
+  r.tested = f.tested;
+  r.bad_cus = f.bad;
+  r.verified = f.verified;
+  for (int x = 0; x < 8; ++x) r.per_xcd[x] = f.per_xcd[x];
+  r.ms = c.lds.sets.end();
   return r;
 }
 

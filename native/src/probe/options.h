@@ -56,7 +56,32 @@ inline bool opt_ints(const char* json, const char* key, long long* out, int n) {
   return true;
 }
 
+// An integer option clamped to [lo, hi].
+inline int opt_clamped(const char* json, const char* key, long long lo, long long hi, long long def) {
+  return static_cast<int>(std::min(hi, std::max(lo, opt_int(json, key, def))));
+}
+
+// An index option: the value when in [0, n), else -1 (a test hook that is off).
+inline int opt_index(const char* json, const char* key, long long n) {
+  const long long v = opt_int(json, key, -1);
+  return v >= 0 && v < n ? static_cast<int>(v) : -1;
+}
+
+// A dump stage: 1..max, anything else 0 (no dump).
+inline int opt_stage(const char* json, const char* key, long long max) {
+  const long long v = opt_int(json, key, 0);
+  return v >= 1 && v <= max ? static_cast<int>(v) : 0;
+}
+
+// A salt option: whether the caller gave one (>= 0), and its value.
+inline void opt_salt(const char* json, const char* key, bool* given, uint32_t* salt) {
+  const long long v = opt_int(json, key, -1);
+  *given = v >= 0;
+  *salt = *given ? static_cast<uint32_t>(v) : 0u;
+}
+
 constexpr long long kMaxPatterns = 4;
+constexpr long long kMaxInjectFlips = 4096;  // "injectBitFlips" of the probe, the peer checks and the sweep
 
 // Default pattern (probe option "hbmPattern" selects per run, for in-process A/B). Measured on
 // MI355X, 9 interleaved rounds (profiles/r3h_probe_pattern_ab.json): 1 GiB test 6.16 -> 6.41 TB/s
@@ -156,10 +181,10 @@ struct Plan {
   static Plan parse(const char* json, int dev, uint64_t bytes) {
     Plan pl;
     pl.n16 = bytes / 16;
-    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "hostLinkPatterns", 2))));
+    pl.patterns = opt_clamped(json, "hostLinkPatterns", 1, kMaxPatterns, 2);
     pl.seed = 0x4C4B0000u + static_cast<uint32_t>(dev);
     pl.inject_chunk = opt_int(json, "injectHostLinkFlipAtChunk", -1);
-    pl.grid = static_cast<int>(std::min<long long>(kMaxGrid, std::max(1LL, opt_int(json, "hostLinkGrid", kGrid))));
+    pl.grid = opt_clamped(json, "hostLinkGrid", 1, kMaxGrid, kGrid);
     pl.unroll = static_cast<int>(opt_int(json, "hostLinkUnroll", kUnroll));
     pl.nt = opt_bool(json, "hostLinkNT", kNonTemporal);
     pl.coherent = opt_bool(json, "hostLinkCoherent", kCoherent);
@@ -216,6 +241,7 @@ struct Plan {
   int fault_xcc = -1;         // test hook "injectLdsFaultXcc": the flip only on that XCD
   long long skip_chunk = -1;  // test hook "injectLdsSkipChunk"
   int dump_stage = 0;         // "ldsDumpStage" 1 | 2 | 3, only with a caller buffer
+  bool on() const { return n16 != 0; }
   uint32_t stride() const { return stride_for(n16 * 4); }
   // "ldsBytes": 16 .. kBytesPerCU, rounded down to whole chunks; anything else throws.
   static Plan parse(const char* json, int dev) {
@@ -224,18 +250,14 @@ struct Plan {
     if (bytes < 16 || bytes > static_cast<long long>(kBytesPerCU))
       throw std::invalid_argument("ldsBytes outside [16, 163840]");
     pl.n16 = static_cast<uint32_t>(bytes / 16);
-    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "ldsPatterns", 2))));
-    const long long salt = opt_int(json, "ldsSalt", -1);
-    pl.salt_given = salt >= 0;
-    pl.salt = pl.salt_given ? static_cast<uint32_t>(salt) : 0u;
+    pl.patterns = opt_clamped(json, "ldsPatterns", 1, kMaxPatterns, 2);
+    opt_salt(json, "ldsSalt", &pl.salt_given, &pl.salt);
     pl.seed = 0x4C445300u + static_cast<uint32_t>(dev);
-    pl.blocks_per_cu =
-        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "ldsBlocksPerCU", kBlocksPerCU))));
+    pl.blocks_per_cu = opt_clamped(json, "ldsBlocksPerCU", 1, kMaxBlocksPerCU, kBlocksPerCU);
     pl.flip_byte = opt_int(json, "injectLdsFlipAtByte", -1);
     pl.fault_xcc = static_cast<int>(opt_int(json, "injectLdsFaultXcc", -1));
     pl.skip_chunk = opt_int(json, "injectLdsSkipChunk", -1);
-    const long long stage = opt_int(json, "ldsDumpStage", 0);
-    pl.dump_stage = stage >= 1 && stage <= 3 ? static_cast<int>(stage) : 0;
+    pl.dump_stage = opt_stage(json, "ldsDumpStage", 3);
     return pl;
   }
 };
@@ -288,13 +310,10 @@ struct Plan {
   static Plan parse(const char* json, int dev) {
     Plan pl;
     pl.on = true;
-    pl.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "regsPatterns", 2))));
-    const long long salt = opt_int(json, "regsSalt", -1);
-    pl.salt_given = salt >= 0;
-    pl.salt = pl.salt_given ? static_cast<uint32_t>(salt) : 0u;
+    pl.patterns = opt_clamped(json, "regsPatterns", 1, kMaxPatterns, 2);
+    opt_salt(json, "regsSalt", &pl.salt_given, &pl.salt);
     pl.seed = 0x52454700u + static_cast<uint32_t>(dev);
-    pl.blocks_per_cu =
-        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "regsBlocksPerCU", kBlocksPerCU))));
+    pl.blocks_per_cu = opt_clamped(json, "regsBlocksPerCU", 1, kMaxBlocksPerCU, kBlocksPerCU);
     long long f[3];
     if (opt_ints(json, "injectRegFlip", f, 3) && f[0] >= 0 && f[0] < kRegistersPerLane && f[1] >= 0 && f[1] < kLanes &&
         f[2] >= 0 && f[2] < 32) {
@@ -302,14 +321,10 @@ struct Plan {
       pl.flip_lane = static_cast<int>(f[1]);
       pl.flip_bit = static_cast<int>(f[2]);
     }
-    const long long simd = opt_int(json, "injectRegFaultSimd", -1);
-    pl.fault_simd = simd >= 0 && simd < kSimdsPerCU ? static_cast<int>(simd) : -1;
-    const long long xcc = opt_int(json, "injectRegFaultXcc", -1);
-    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
-    const long long skip = opt_int(json, "injectRegSkip", -1);
-    pl.skip_u = skip >= 0 && skip < kRegistersPerLane ? static_cast<int>(skip) : -1;
-    const long long stage = opt_int(json, "regsDumpStage", 0);
-    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    pl.fault_simd = opt_index(json, "injectRegFaultSimd", kSimdsPerCU);
+    pl.fault_xcc = opt_index(json, "injectRegFaultXcc", 8);
+    pl.skip_u = opt_index(json, "injectRegSkip", kRegistersPerLane);
+    pl.dump_stage = opt_stage(json, "regsDumpStage", 2);
     return pl;
   }
 };
@@ -375,9 +390,8 @@ struct Plan {
   static Plan parse(const char* json, int dev) {
     Plan pl;
     pl.on = true;
-    pl.iters = static_cast<int>(std::min<long long>(kMaxIters, std::max(1LL, opt_int(json, "aluIters", kIters))));
-    pl.blocks_per_cu =
-        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "aluBlocksPerCU", kBlocksPerCU))));
+    pl.iters = opt_clamped(json, "aluIters", 1, kMaxIters, kIters);
+    pl.blocks_per_cu = opt_clamped(json, "aluBlocksPerCU", 1, kMaxBlocksPerCU, kBlocksPerCU);
     const long long seed = opt_int(json, "aluSeed", -1);
     pl.seed = seed >= 0 ? static_cast<uint32_t>(seed) : kPlanSeedBase + static_cast<uint32_t>(dev);
     long long f[4];
@@ -388,12 +402,9 @@ struct Plan {
       pl.flip_lane = static_cast<int>(f[2]);
       pl.flip_bit = static_cast<int>(f[3]);
     }
-    const long long simd = opt_int(json, "injectAluFaultSimd", -1);
-    pl.fault_simd = simd >= 0 && simd < kSimdsPerCU ? static_cast<int>(simd) : -1;
-    const long long xcc = opt_int(json, "injectAluFaultXcc", -1);
-    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
-    const long long stage = opt_int(json, "aluDumpStage", 0);
-    pl.dump_stage = stage >= 1 && stage <= 3 ? static_cast<int>(stage) : 0;
+    pl.fault_simd = opt_index(json, "injectAluFaultSimd", kSimdsPerCU);
+    pl.fault_xcc = opt_index(json, "injectAluFaultXcc", 8);
+    pl.dump_stage = opt_stage(json, "aluDumpStage", 3);
     return pl;
   }
   // what the caller's buffer receives: the digests (stages 1 and 2) or the trans trace (stage 3)
@@ -461,16 +472,14 @@ struct Plan {
   static Plan parse(const char* json, int dev) {
     Plan pl;
     pl.on = true;
-    pl.iters = static_cast<int>(std::min<long long>(kMaxIters, std::max(1LL, opt_int(json, "atomIters", kIters))));
-    pl.blocks_per_cu =
-        static_cast<int>(std::min<long long>(kMaxBlocksPerCU, std::max(1LL, opt_int(json, "atomBlocksPerCU", kBlocksPerCU))));
+    pl.iters = opt_clamped(json, "atomIters", 1, kMaxIters, kIters);
+    pl.blocks_per_cu = opt_clamped(json, "atomBlocksPerCU", 1, kMaxBlocksPerCU, kBlocksPerCU);
     const long long layers = opt_int(json, "atomLayers", kLayerMask);
     pl.layers = layers >= 1 && layers <= kLayerMask ? static_cast<int>(layers) : kLayerMask;
     const long long seed = opt_int(json, "atomSeed", -1);
     pl.seed = seed >= 0 ? static_cast<uint32_t>(seed) : kPlanSeedBase + static_cast<uint32_t>(dev);
     pl.time_kernels = opt_bool(json, "atomTimeKernels", false);
-    const long long stage = opt_int(json, "atomDumpStage", 0);
-    pl.dump_stage = stage >= 1 && stage <= 2 ? static_cast<int>(stage) : 0;
+    pl.dump_stage = opt_stage(json, "atomDumpStage", 2);
     // which (layer, op) pairs exist: the returning ops and the ticket test not in the dev layer
     // layer 3 in a hook: the lds layer's second addressing (slot = lane & 15), contended ops only
     auto known = [](long long layer, long long op, bool ticket_ok) {
@@ -494,10 +503,8 @@ struct Plan {
       pl.flip_lane = static_cast<int>(f[3]);
       pl.flip_bit = static_cast<int>(f[4]);
     }
-    const long long xcc = opt_int(json, "injectAtomFaultXcc", -1);
-    pl.fault_xcc = xcc >= 0 && xcc < 8 ? static_cast<int>(xcc) : -1;
-    const long long wg = opt_int(json, "injectAtomFaultWorkgroup", -1);
-    pl.fault_wg = wg >= 0 && wg < kMaxBlocksPerCU * 256 ? static_cast<int>(wg) : -1;
+    pl.fault_xcc = opt_index(json, "injectAtomFaultXcc", 8);
+    pl.fault_wg = opt_index(json, "injectAtomFaultWorkgroup", kMaxBlocksPerCU * 256);
     return pl;
   }
 };
@@ -566,17 +573,27 @@ struct ProbeOptions {
   atom::Plan atom;                 // "atomCheck"; !on: off, and none of its options is looked up
   bool atom_first = atom::kFirst == 1;  // "atomFirst": as "ldsFirst"
 
+  // An opt-in per-CU phase: off, and none of its options looked up, unless ``check_key`` is set.
+  // ``first`` comes in as the phase's measured default.
+  template <class Plan>
+  static void check(const char* json, int dev, const char* check_key, const char* first_key, Plan* plan, bool* first) {
+    if (!opt_bool(json, check_key, false)) return;
+    *plan = Plan::parse(json, dev);
+    plan->dump_stage = 0;  // the dump needs the caller buffer of the phase's own entry point
+    *first = opt_int(json, first_key, *first) == 1;
+  }
+
   static ProbeOptions parse(const char* json, int dev = 0) {
     ProbeOptions o;
     o.hbm_bytes = static_cast<uint64_t>(opt_int(json, "hbmBytes", 1LL << 30));
-    o.patterns = static_cast<int>(std::min(kMaxPatterns, std::max(1LL, opt_int(json, "patterns", 2))));
+    o.patterns = opt_clamped(json, "patterns", 1, kMaxPatterns, 2);
     o.cheap_pattern = opt_int(json, "hbmPattern", kHbmPattern) == 1;
     o.tiled = o.cheap_pattern && opt_int(json, "hbmLayout", kHbmLayout) == 1;
     o.fill_blocks_per_cu =
         std::max(1LL, opt_int(json, "hbmFillBlocksPerCU", opt_int(json, "hbmBlocksPerCU", kHbmFillBlocksPerCU)));
     o.verify_blocks_per_cu =
         std::max(1LL, opt_int(json, "hbmVerifyBlocksPerCU", opt_int(json, "hbmBlocksPerCU", kHbmVerifyBlocksPerCU)));
-    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    o.inject_flips = opt_clamped(json, "injectBitFlips", 0, kMaxInjectFlips, 0);
     o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
     o.mfma = opt_bool(json, "mfma", true);
     o.gemm_n = std::max(256, (static_cast<int>(opt_int(json, "gemmN", 4096)) / 256) * 256);
@@ -602,27 +619,11 @@ struct ProbeOptions {
       o.host_link = hostlink::Plan::parse(json, dev, hl_bytes);
       o.host_link_on_mfma_stream = o.overlap && opt_int(json, "hostLinkStream", 0) == 1;
     }
-    if (opt_bool(json, "ldsCheck", false)) {
-      o.lds = lds::Plan::parse(json, dev);
-      o.lds.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_lds
-      o.lds_first = opt_int(json, "ldsFirst", lds::kFirst) == 1;
-    }
-    if (opt_bool(json, "regCheck", false)) {
-      o.regs = regs::Plan::parse(json, dev);
-      o.regs.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_regs
-      o.regs_first = opt_int(json, "regsFirst", regs::kFirst) == 1;
-    }
-    if (opt_bool(json, "aluCheck", false)) {
-      o.alu = alu::Plan::parse(json, dev);
-      o.alu.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_alu
-      o.alu_first = opt_int(json, "aluFirst", alu::kFirst) == 1;
-    }
-    if (opt_bool(json, "atomCheck", false)) {
-      o.atom = atom::Plan::parse(json, dev);
-      o.atom.dump_stage = 0;  // the dump needs the caller buffer of mi355x_probe_atomics
-      o.atom.time_kernels = false;  // the claim probe records no event between the kernels
-      o.atom_first = opt_int(json, "atomFirst", atom::kFirst) == 1;
-    }
+    check(json, dev, "ldsCheck", "ldsFirst", &o.lds, &o.lds_first);
+    check(json, dev, "regCheck", "regsFirst", &o.regs, &o.regs_first);
+    check(json, dev, "aluCheck", "aluFirst", &o.alu, &o.alu_first);
+    check(json, dev, "atomCheck", "atomFirst", &o.atom, &o.atom_first);
+    o.atom.time_kernels = false;  // the claim probe records no event between the kernels
     return o;
   }
 };
@@ -663,8 +664,8 @@ struct PeerOptions {
     PeerOptions o;
     o.bytes = peer_bytes(json, def_bytes);
     o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
-    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
-    o.inject_link = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectLink", 0))));
+    o.inject_flips = opt_clamped(json, "injectBitFlips", 0, kMaxInjectFlips, 0);
+    o.inject_link = opt_clamped(json, "injectLink", 0, 4096, 0);
     o.skip_copy = opt_bool(json, "skipCopy", false);
     return o;
   }
@@ -688,7 +689,7 @@ struct SweepOptions {
     o.reserve = static_cast<uint64_t>(std::max(0LL, opt_int(json, "reserve", 4LL << 30)));
     o.offset = static_cast<uint64_t>(std::max(0LL, opt_int(json, "offset", 0)));
     o.keep = opt_bool(json, "keep", false);
-    o.inject_flips = static_cast<int>(std::min(4096LL, std::max(0LL, opt_int(json, "injectBitFlips", 0))));
+    o.inject_flips = opt_clamped(json, "injectBitFlips", 0, kMaxInjectFlips, 0);
     o.inject_chunk = opt_int(json, "injectFlipAtChunk", -1);
     return o;
   }

@@ -25,7 +25,7 @@
 //   arena.h          the layout of the probe's one allocation (pure host, unit-tested)
 //   report.h         result structs -> the JSON reports (pure host, unit-tested)
 //   hbm.h            pattern kernels and the pattern pass shared by probe, peer checks and sweep
-//   census.h         CU identity and the per-CU MFMA census
+//   census.h         CU identity, the per-CU MFMA census, and the CU-map fold of the per-CU phases
 //   gemm_bf16.h      the production GEMM kernel; gemm_bf16_lab.h its A/B siblings
 //   abft.h           operand generation, VALU reference, ABFT checksums
 //   mfma_phase.h     the GEMM dispatch and the bf16 MFMA phase (launch / finish)
@@ -35,7 +35,9 @@
 //   regfile.h        per-SIMD vector register file march ("regCheck")
 //   alu.h            per-SIMD vector-ALU instruction program ("aluCheck"); alu_ref.h its host expectation
 //   atomics.h        LDS, L2 and device-scope atomic units ("atomCheck"); atomics_ref.h its host expectation
-//   ctx.h            per-device state and ensure_ctx(); peer.h the xGMI checks; sweep.h the HBM sweep
+//   ctx.h            per-device state, ensure_ctx() and CounterSets, the two counter sets (and their
+//                    make / reset / run / end protocol) that each of the four phases above keeps
+//   peer.h           the xGMI checks; sweep.h the HBM sweep
 //   sweep_window.h   a sweep window split over the buffer's chunks (pure host, unit-tested)
 #include <hip/hip_runtime.h>
 
@@ -180,6 +182,18 @@ void enqueue_hbm(DeviceCtx& ctx, const PatternPass& pass, const ProbeOptions& o,
   PROBE_CHECK(hipMemcpyAsync(ctx.host_res, cnt, 2 * o.patterns * sizeof(unsigned long long), hipMemcpyDeviceToHost, pass.s));
 }
 
+// One opt-in per-CU phase of a claim probe (lds.h, regfile.h, alu.h, atomics.h share the shape
+// ensure / launch / finish): its plan, whether it goes ahead of the MFMA phase on that phase's
+// stream, where its result goes in the report, and whether it is still to be enqueued.
+template <class Plan, class Result>
+struct Check {
+  Plan plan;
+  bool on, first;
+  bool* has;
+  Result* out;
+  bool pending = on;
+};
+
 std::string run_probe(int dev, const char* opts) {
   const ProbeOptions o = ProbeOptions::parse(opts, dev);
   auto t0 = std::chrono::steady_clock::now();
@@ -191,15 +205,21 @@ std::string run_probe(int dev, const char* opts) {
     hl.alloc_ms = hostlink::ensure(ctx, hl.n16 * 16, hl.coherent);
     hl_s = host_link_stream(ctx, o);
   }
-  lds::Plan ld = o.lds;
-  if (ld.n16) lds::ensure(ctx, false);
-  regs::Plan rg = o.regs;
-  if (rg.on) regs::ensure(ctx, rg.test_kernel(), false);
-  alu::Plan al = o.alu;
-  if (al.on) alu::ensure(ctx, al, 0);
-  atom::Plan at = o.atom;
-  if (at.on) atom::ensure(ctx, at, false);
   ProbeReport rep;
+  // the opt-in per-CU phases, in the order they are enqueued, finished and reported
+  Check<lds::Plan, LdsResult> ld{o.lds, o.lds.on(), o.lds_first, &rep.has_lds, &rep.lds};
+  Check<regs::Plan, RegsResult> rg{o.regs, o.regs.on, o.regs_first, &rep.has_regs, &rep.regs};
+  Check<alu::Plan, AluResult> al{o.alu, o.alu.on, o.alu_first, &rep.has_alu, &rep.alu};
+  Check<atom::Plan, AtomResult> at{o.atom, o.atom.on, o.atom_first, &rep.has_atom, &rep.atom};
+  auto each_check = [&](auto&& f) {
+    f(ld);
+    f(rg);
+    f(al);
+    f(at);
+  };
+  each_check([&](auto& c) {
+    if (c.pending) ensure(ctx, c.plan);
+  });
   PhaseTimes& t = rep.phases;
   t.hbm_first = o.hbm_first;
   t.setup_ms = ms_since(t0);
@@ -223,51 +243,26 @@ std::string run_probe(int dev, const char* opts) {
   auto t_run = std::chrono::steady_clock::now();
   reset_counters(ctx, o, cnt, s, s2);
   const lowp::Phase lp = lowp_phase(ctx, o, base, lay);
-  bool lds_pending = ld.n16 != 0;
-  auto enqueue_lds = [&](bool here) {
-    if (!lds_pending || !here) return;
-    lds::launch(ctx, s2, ld);
-    lds_pending = false;
-  };
-  bool regs_pending = rg.on;
-  auto enqueue_regs = [&](bool here) {
-    if (!regs_pending || !here) return;
-    regs::launch(ctx, s2, rg);
-    regs_pending = false;
-  };
-  bool alu_pending = al.on;
-  auto enqueue_alu = [&](bool here) {
-    if (!alu_pending || !here) return;
-    alu::launch(ctx, s2, al);
-    alu_pending = false;
-  };
-  bool atom_pending = at.on;
-  auto enqueue_atom = [&](bool here) {
-    if (!atom_pending || !here) return;
-    atom::launch(ctx, s2, at);
-    atom_pending = false;
+  // ``ahead``: only the phases that go ahead of the MFMA phase; else every one still pending
+  auto enqueue_checks = [&](bool ahead) {
+    each_check([&](auto& c) {
+      if (!c.pending || (ahead && !c.first)) return;
+      launch(ctx, s2, c.plan);
+      c.pending = false;
+    });
   };
   auto enqueue_mfma = [&](int when) {
     if (!o.mfma || o.hbm_first != when) return;
-    enqueue_lds(o.overlap && o.lds_first);
-    enqueue_regs(o.overlap && o.regs_first);
-    enqueue_alu(o.overlap && o.alu_first);
-    enqueue_atom(o.overlap && o.atom_first);
+    if (o.overlap) enqueue_checks(true);
     launch_mfma_phase(base, lay, o, ctx, s2);
     lowp::launch(s2, lp);
-    enqueue_lds(o.overlap);
-    enqueue_regs(o.overlap);
-    enqueue_alu(o.overlap);
-    enqueue_atom(o.overlap);
+    if (o.overlap) enqueue_checks(false);
   };
   const PatternPass pass = hbm_pass(ctx, o, dev, base, lay, n16);
   enqueue_mfma(0);
   enqueue_hbm(ctx, pass, o, cnt, [&] { enqueue_mfma(2); });
   enqueue_mfma(1);
-  enqueue_lds(true);  // serial, or no MFMA phase to follow
-  enqueue_regs(true);
-  enqueue_alu(true);
-  enqueue_atom(true);
+  enqueue_checks(false);  // serial, or no MFMA phase to follow
   if (hl.n16) hostlink::launch(ctx, hl_s, hl);
   t.launch_ms = ms_since(t_run);  // host time to enqueue the whole probe
 
@@ -282,26 +277,11 @@ std::string run_probe(int dev, const char* opts) {
     PROBE_CHECK(hipStreamSynchronize(s2));
     finish_mfma(o, ctx, &rep.mfma, &rep.cus);
   }
-  rep.has_lds = ld.n16 != 0;
-  if (ld.n16) {
-    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
-    rep.lds = lds::finish(ctx, ld, o.require_all_cus);
-  }
-  rep.has_regs = rg.on;
-  if (rg.on) {
-    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
-    rep.regs = regs::finish(ctx, rg, o.require_all_cus);
-  }
-  rep.has_alu = al.on;
-  if (al.on) {
-    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
-    rep.alu = alu::finish(ctx, al, o.require_all_cus);
-  }
-  rep.has_atom = at.on;
-  if (at.on) {
-    if (!o.mfma && s2 != s) PROBE_CHECK(hipStreamSynchronize(s2));
-    rep.atom = atom::finish(ctx, at, o.require_all_cus);
-  }
+  if (!o.mfma && s2 != s && (ld.on || rg.on || al.on || at.on)) PROBE_CHECK(hipStreamSynchronize(s2));
+  each_check([&](auto& c) {
+    *c.has = c.on;
+    if (c.on) *c.out = finish(ctx, c.plan, o.require_all_cus);
+  });
   rep.lowp = lowp::finish(lp, o.require_all_cus);
   t.mfma_wall_ms = o.mfma ? ms_since(t_run) : 0.0;
   rep.has_host_link = hl.n16 != 0;
@@ -436,6 +416,35 @@ void launch_generator(hipStream_t s, int dtype, void* out, uint64_t count, uint8
     hipLaunchKernelGGL(lowp::gen_operand<lowp::MxFp8>, grid, block, 0, s, words, count / 4, scales, count / 32, seed, arg);
   else
     hipLaunchKernelGGL(lowp::gen_operand<lowp::MxFp4>, grid, block, 0, s, words, count / 8, scales, count / 32, seed, arg);
+}
+
+// A per-CU phase alone, on the HBM stream: what mi355x_probe_lds / _regs / _alu / _atomics share.
+// ``block``: the phase's report block; ``dump_of``: where a dump run left its device copy, and how
+// much of it the caller's buffer receives.
+struct Dump {
+  const void* dev;
+  size_t bytes;
+};
+template <class Plan, class Block, class DumpOf>
+char* run_check(int dev, const char* opts_json, void* buf, size_t buf_bytes, Block&& block, DumpOf&& dump_of) {
+  if (!device_ok(dev)) return bad_device();
+  ProbeActive active;
+  std::lock_guard<std::mutex> g(device_mutex(dev));
+  return guarded(device_head(dev), [&] {
+    Plan pl = Plan::parse(opts_json, dev);  // lds: throws on a size outside [16, 163840]
+    if (!buf || !buf_bytes) pl.dump_stage = 0;
+    DeviceCtx& ctx = ensure_ctx(dev);
+    ensure(ctx, pl);
+    launch(ctx, ctx.stream, pl);
+    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
+    const auto r = finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
+    if (pl.dump_stage) {
+      const Dump d = dump_of(ctx, pl);
+      PROBE_CHECK(hipMemcpy(buf, d.dev, std::min(buf_bytes, d.bytes), hipMemcpyDeviceToHost));
+    }
+    // the block is the whole report, with the usual head
+    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + block(r).substr(1);
+  });
 }
 
 }  // namespace
@@ -794,80 +803,26 @@ int mi355x_probe_gemm_bf16(int dev, const void* A, const void* Bt, void* C, int 
 }
 
 char* mi355x_probe_lds(int dev, const char* opts_json, void* image, size_t image_bytes) {
-  if (!device_ok(dev)) return bad_device();
-  ProbeActive active;
-  std::lock_guard<std::mutex> g(device_mutex(dev));
-  return guarded(device_head(dev), [&] {
-    lds::Plan pl = lds::Plan::parse(opts_json, dev);  // throws on a size outside [16, 163840]
-    if (!image || !image_bytes) pl.dump_stage = 0;
-    DeviceCtx& ctx = ensure_ctx(dev);
-    lds::ensure(ctx, pl.dump_stage != 0);
-    lds::launch(ctx, ctx.stream, pl);
-    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
-    const LdsResult r = lds::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
-    if (pl.dump_stage)
-      PROBE_CHECK(hipMemcpy(image, ctx.lds_dump, std::min<size_t>(image_bytes, static_cast<size_t>(pl.n16) * 16),
-                            hipMemcpyDeviceToHost));
-    // the block is the whole report, with the usual head
-    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + lds_block(r).substr(1);
+  return run_check<lds::Plan>(dev, opts_json, image, image_bytes, lds_block, [](DeviceCtx& ctx, const lds::Plan& pl) {
+    return Dump{ctx.lds.dump, static_cast<size_t>(pl.n16) * 16};
   });
 }
 
 char* mi355x_probe_regs(int dev, const char* opts_json, void* image, size_t image_bytes) {
-  if (!device_ok(dev)) return bad_device();
-  ProbeActive active;
-  std::lock_guard<std::mutex> g(device_mutex(dev));
-  return guarded(device_head(dev), [&] {
-    regs::Plan pl = regs::Plan::parse(opts_json, dev);
-    if (!image || !image_bytes) pl.dump_stage = 0;
-    DeviceCtx& ctx = ensure_ctx(dev);
-    regs::ensure(ctx, pl.test_kernel(), pl.dump_stage != 0);
-    regs::launch(ctx, ctx.stream, pl);
-    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
-    const RegsResult r = regs::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
-    if (pl.dump_stage)
-      PROBE_CHECK(hipMemcpy(image, ctx.regs_dump, std::min<size_t>(image_bytes, regs::kImageBytes), hipMemcpyDeviceToHost));
-    // the block is the whole report, with the usual head
-    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + regs_block(r).substr(1);
+  return run_check<regs::Plan>(dev, opts_json, image, image_bytes, regs_block, [](DeviceCtx& ctx, const regs::Plan&) {
+    return Dump{ctx.regs.dump, regs::kImageBytes};
   });
 }
 
 char* mi355x_probe_alu(int dev, const char* opts_json, void* dump, size_t dump_bytes) {
-  if (!device_ok(dev)) return bad_device();
-  ProbeActive active;
-  std::lock_guard<std::mutex> g(device_mutex(dev));
-  return guarded(device_head(dev), [&] {
-    alu::Plan pl = alu::Plan::parse(opts_json, dev);
-    if (!dump || !dump_bytes) pl.dump_stage = 0;
-    DeviceCtx& ctx = ensure_ctx(dev);
-    alu::ensure(ctx, pl, pl.dump_stage);
-    alu::launch(ctx, ctx.stream, pl);
-    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
-    const AluResult r = alu::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
-    if (pl.dump_stage)
-      PROBE_CHECK(hipMemcpy(dump, pl.dump_stage == 3 ? ctx.alu_trace : ctx.alu_dump, std::min<size_t>(dump_bytes, pl.dump_bytes()),
-                            hipMemcpyDeviceToHost));
-    // the block is the whole report, with the usual head
-    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + alu_block(r).substr(1);
+  return run_check<alu::Plan>(dev, opts_json, dump, dump_bytes, alu_block, [](DeviceCtx& ctx, const alu::Plan& pl) {
+    return Dump{pl.dump_stage == 3 ? ctx.alu.trace : ctx.alu.dump, pl.dump_bytes()};
   });
 }
 
 char* mi355x_probe_atomics(int dev, const char* opts_json, void* dump, size_t dump_bytes) {
-  if (!device_ok(dev)) return bad_device();
-  ProbeActive active;
-  std::lock_guard<std::mutex> g(device_mutex(dev));
-  return guarded(device_head(dev), [&] {
-    atom::Plan pl = atom::Plan::parse(opts_json, dev);
-    if (!dump || !dump_bytes) pl.dump_stage = 0;
-    DeviceCtx& ctx = ensure_ctx(dev);
-    atom::ensure(ctx, pl, pl.dump_stage != 0);
-    atom::launch(ctx, ctx.stream, pl);
-    PROBE_CHECK(hipStreamSynchronize(ctx.stream));
-    const AtomResult r = atom::finish(ctx, pl, opt_bool(opts_json, "requireAllCUs", true));
-    if (pl.dump_stage)
-      PROBE_CHECK(hipMemcpy(dump, ctx.atom_dump, std::min<size_t>(dump_bytes, atom::kDumpBytes), hipMemcpyDeviceToHost));
-    // the block is the whole report, with the usual head
-    return "{" + device_head(dev) + ",\"passed\":" + jbool(r.ok()) + "," + atom_block(r).substr(1);
+  return run_check<atom::Plan>(dev, opts_json, dump, dump_bytes, atom_block, [](DeviceCtx& ctx, const atom::Plan&) {
+    return Dump{ctx.atom.dump, atom::kDumpBytes};
   });
 }
 

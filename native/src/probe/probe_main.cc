@@ -19,10 +19,15 @@ int main(int argc, char** argv) {
   int device = -1;
   int lowp_mask = 0;  // "mfmaLowPrecision": bit 0 fp8, 1 mxfp8, 2 mxfp4
   long long host_link = 0;  // "hostLinkBytes": the PCIe host-link phase (0 = off)
-  bool lds_check = false;   // "ldsCheck": the per-CU LDS phase
-  bool reg_check = false;   // "regCheck": the per-SIMD register-file phase
-  bool alu_check = false;   // "aluCheck": the per-SIMD vector-ALU phase
-  bool atom_check = false;  // "atomCheck": the atomic-unit phase
+  // the opt-in per-CU phases: the flag, the library's option, whether the flag was given
+  struct {
+    const char* flag;
+    const char* option;
+    bool on;
+  } checks[] = {{"--lds-check", "ldsCheck", false},       // the per-CU LDS phase
+                {"--register-check", "regCheck", false},  // the per-SIMD register-file phase
+                {"--alu-check", "aluCheck", false},       // the per-SIMD vector-ALU phase
+                {"--atomics-check", "atomCheck", false}}; // the atomic-unit phase
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* {
@@ -32,7 +37,10 @@ int main(int argc, char** argv) {
       }
       return argv[++i];
     };
-    if (a == "--device") {
+    const auto check = std::find_if(std::begin(checks), std::end(checks), [&](const auto& c) { return a == c.flag; });
+    if (check != std::end(checks)) {
+      check->on = true;
+    } else if (a == "--device") {
       device = std::atoi(next());
       all = false;
     } else if (a == "--all") {
@@ -59,14 +67,6 @@ int main(int argc, char** argv) {
       }
     } else if (a == "--host-link-bytes") {
       host_link = std::atoll(next());
-    } else if (a == "--lds-check") {
-      lds_check = true;
-    } else if (a == "--register-check") {
-      reg_check = true;
-    } else if (a == "--alu-check") {
-      alu_check = true;
-    } else if (a == "--atomics-check") {
-      atom_check = true;
     } else if (a == "--list") {
       list = true;
     } else if (a == "-h" || a == "--help") {
@@ -110,10 +110,8 @@ int main(int argc, char** argv) {
                        ",\"gemmN\":" + std::to_string(gemm_n);
   if (lowp_mask) opts_s += ",\"mfmaLowPrecision\":" + std::to_string(lowp_mask);
   if (host_link > 0) opts_s += ",\"hostLinkBytes\":" + std::to_string(host_link);
-  if (lds_check) opts_s += ",\"ldsCheck\":1";
-  if (reg_check) opts_s += ",\"regCheck\":1";
-  if (alu_check) opts_s += ",\"aluCheck\":1";
-  if (atom_check) opts_s += ",\"atomCheck\":1";
+  for (const auto& c : checks)
+    if (c.on) opts_s += std::string(",\"") + c.option + "\":1";
   opts_s += "}";
   const char* opts = opts_s.c_str();
   std::vector<std::string> results(devs.size());

@@ -46,8 +46,8 @@
 #include <cstdint>
 
 #include "arena.h"    // kCuMapWords
-#include "census.h"   // cu_key, simd_id, count_cus
-#include "ctx.h"      // DeviceCtx: the phase's events, counters and pinned result
+#include "census.h"   // cu_key, simd_id, fold_cus, decode_dump
+#include "ctx.h"      // DeviceCtx, CounterSets: the phase's events, counters and pinned result
 #include "hbm.h"      // pattern16, umin64
 #include "options.h"  // regs::Plan
 #include "report.h"   // RegsResult
@@ -58,7 +58,7 @@ namespace regs {
 
 constexpr int kThreads = 256;
 
-// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (see lds.h).
+// One set of counters; two sets, and workgroup 0 of a run resets the OTHER set (ctx.h CounterSets).
 constexpr int kSlotBadBits = 0, kSlotFirstBad = 1, kSlotWorkgroups = 2, kSlotSimdShort = 3, kSlotDumpCu = 4,
               kSlotDumpSimds = 5, kSlotTested = 6, kSlotBad = kSlotTested + kCuMapWords,
               kSlots = kSlotBad + kCuMapWords;
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(kThreads) void rf_march(const KernelArgs a) {
 // once per context; finish() fails the phase unless they are 512 and 1.
 template <bool kTest>
 inline void ensure_attr(DeviceCtx& c) {
-  int* at = c.regs_attr[kTest ? 1 : 0];
+  int* at = c.regs.attr[kTest ? 1 : 0];
   if (at[0]) return;
   hipFuncAttributes fa{};
   PROBE_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&rf_march<kTest>)));
@@ -298,36 +298,25 @@ inline void ensure_attr(DeviceCtx& c) {
   at[0] = fa.numRegs;
 }
 
-// Makes the phase's events, counter sets and pinned result (and, ``want_dump``, the device image of
-// one workgroup's registers), and puts both counter sets at their reset values unless the last run
-// left them so.
-inline void ensure(DeviceCtx& c, bool test_kernel, bool want_dump) {
-  if (!c.regs_res) {  // set last: a failure half way is picked up by the next probe that asks
-    for (auto& e : c.regs_ev)
-      if (!e) PROBE_CHECK(hipEventCreate(&e));
-    if (!c.regs_cnt) PROBE_CHECK(hipMalloc(reinterpret_cast<void**>(&c.regs_cnt), 2 * kSlots * sizeof(unsigned long long)));
-    PROBE_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.regs_res), kSlots * sizeof(unsigned long long)));
-    c.regs_clean = false;
-  }
-  if (test_kernel) ensure_attr<true>(c);
+// Makes the phase's counter sets (and, for a dump stage, the device image of one workgroup's
+// registers), and puts both sets at their reset values unless the last run left them so.
+inline void ensure(DeviceCtx& c, const Plan& pl) {
+  CounterSets& cs = c.regs.sets;
+  cs.make(kSlots);
+  if (pl.test_kernel()) ensure_attr<true>(c);
   else ensure_attr<false>(c);
-  if (!c.regs_clean) {  // first use, or a run that never reached finish()
-    PROBE_CHECK(hipStreamSynchronize(c.stream));
-    PROBE_CHECK(hipStreamSynchronize(c.stream2));
-    unsigned long long init[2 * kSlots];
-    for (int i = 0; i < 2 * kSlots; ++i) init[i] = reset_value(i % kSlots);
-    PROBE_CHECK(hipMemcpy(c.regs_cnt, init, sizeof init, hipMemcpyHostToDevice));
-    c.regs_set = 0;
-    c.regs_clean = true;
+  if (!cs.clean) {  // first use, or a run that never reached finish()
+    sync_streams(c);
+    cs.reset<kSlots>(reset_value);
   }
-  if (want_dump && !c.regs_dump) PROBE_CHECK(hipMalloc(&c.regs_dump, kImageBytes));
+  if (pl.dump_stage && !c.regs.dump) PROBE_CHECK(hipMalloc(&c.regs.dump, kImageBytes));
 }
 
 // Enqueues the phase on stream s: an event, the kernel, an event, the counters' copy. Settles the
 // plan's salt (the context's run counter unless the caller gave one). No host synchronise.
 inline void launch(DeviceCtx& c, hipStream_t s, Plan& pl) {
-  if (!pl.salt_given) pl.salt = c.regs_runs;
-  ++c.regs_runs;
+  if (!pl.salt_given) pl.salt = c.regs.runs;
+  ++c.regs.runs;
   KernelArgs a{};
   a.seed = pl.seed ^ pl.salt;
   a.patterns = pl.patterns;
@@ -337,26 +326,22 @@ inline void launch(DeviceCtx& c, hipStream_t s, Plan& pl) {
   a.fault_simd = pl.fault_simd;
   a.fault_xcc = pl.fault_xcc;
   a.skip_u = pl.skip_u >= 0 ? static_cast<uint32_t>(pl.skip_u) : ~0u;
-  a.dump_stage = c.regs_dump ? pl.dump_stage : 0;
-  a.dump = static_cast<uint32_t*>(c.regs_dump);
-  a.cnt = c.regs_cnt + c.regs_set * kSlots;
-  a.next = c.regs_cnt + (c.regs_set ^ 1) * kSlots;
+  a.dump_stage = c.regs.dump ? pl.dump_stage : 0;
+  a.dump = static_cast<uint32_t*>(c.regs.dump);
   const int grid = pl.blocks_per_cu * c.prop.multiProcessorCount;
-  c.regs_clean = false;  // until finish() has seen this run end
-  PROBE_CHECK(hipEventRecord(c.regs_ev[0], s));
-  if (pl.test_kernel()) hipLaunchKernelGGL(rf_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
-  else hipLaunchKernelGGL(rf_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
-  PROBE_CHECK(hipEventRecord(c.regs_ev[1], s));
-  PROBE_CHECK(hipGetLastError());
-  PROBE_CHECK(hipMemcpyAsync(c.regs_res, a.cnt, kSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  c.regs.sets.run(s, kSlots, [&](unsigned long long* cnt, unsigned long long* next) {
+    a.cnt = cnt;
+    a.next = next;
+    if (pl.test_kernel()) hipLaunchKernelGGL(rf_march<true>, dim3(grid), dim3(kThreads), 0, s, a);
+    else hipLaunchKernelGGL(rf_march<false>, dim3(grid), dim3(kThreads), 0, s, a);
+  });
 }
 
-// After the stream's synchronise: the counters -> the "regs" block's result; the next run takes the
-// other counter set, which this run's kernel reset.
+// After the stream's synchronise: the counters -> the "regs" block's result.
 inline RegsResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   RegsResult r;
-  const unsigned long long* h = c.regs_res;
-  const int* at = c.regs_attr[pl.test_kernel() ? 1 : 0];
+  const unsigned long long* h = c.regs.sets.res;
+  const int* at = c.regs.attr[pl.test_kernel() ? 1 : 0];
   r.registers_per_lane = at[0];
   r.workgroups_per_cu = at[1];
   r.patterns = pl.patterns;
@@ -367,20 +352,13 @@ inline RegsResult finish(DeviceCtx& c, const Plan& pl, bool require_all) {
   r.simd_short = h[kSlotSimdShort];
   r.bad_bits = h[kSlotBadBits];
   r.first_bad = h[kSlotFirstBad];
-  if (pl.dump_stage && h[kSlotDumpCu] != ~0ull) {
-    r.dump_cu = static_cast<int>(h[kSlotDumpCu]);
-    for (int w = 0; w < 4; ++w) r.dump_simds[w] = static_cast<int>((h[kSlotDumpSimds] >> (8 * w)) & 0xFF);
-  }
-  unsigned long long verified[kCuMapWords];
-  for (int w = 0; w < kCuMapWords; ++w) verified[w] = h[kSlotTested + w] & ~h[kSlotBad + w];
-  r.tested = count_cus(h + kSlotTested).total;
-  r.bad_cus = count_cus(h + kSlotBad).total;
-  const CuCount v = count_cus(verified);
-  r.verified = v.total;
-  for (int x = 0; x < 8; ++x) r.per_xcd[x] = v.per_xcc[x];
-  PROBE_CHECK(hipEventElapsedTime(&r.ms, c.regs_ev[0], c.regs_ev[1]));
-  c.regs_set ^= 1;
-  c.regs_clean = true;
+  if (pl.dump_stage) decode_dump(h[kSlotDumpCu], h[kSlotDumpSimds], &r.dump_cu, r.dump_simds);
+  const CuFold f = fold_cus(h + kSlotTested, h + kSlotBad);
+  r.tested = f.tested;
+  r.bad_cus = f.bad;
+  r.verified = f.verified;
+  for (int x = 0; x < 8; ++x) r.per_xcd[x] = f.per_xcd[x];
+  r.ms = c.regs.sets.end();
   return r;
 }
 

@@ -34,6 +34,25 @@ inline std::string joffset(unsigned long long first_bad, unsigned long long base
   return first_bad == ~0ull ? std::string("null") : std::to_string(base + first_bad * 16);
 }
 
+// "[v0,v1,...]": the per-XCD and per-SIMD counts of the blocks below.
+template <class T>
+inline std::string jarray(const T* v, int n) {
+  std::string out = "[";
+  for (int i = 0; i < n; ++i) out += (i ? "," : "") + std::to_string(v[i]);
+  return out + "]";
+}
+
+// A bit field of a per-CU phase's first_bad key, all-ones = none -> null.
+inline std::string first_bad_field(unsigned long long first_bad, int shift, unsigned long long mask) {
+  return first_bad == ~0ull ? std::string("null") : std::to_string((first_bad >> shift) & mask);
+}
+
+// The tail of a block whose run dumped workgroup 0: its CU key and the SIMD of each of its four waves.
+inline std::string dump_tail(int dump_cu, const int* dump_simds) {
+  if (dump_cu < 0) return "";
+  return ",\"dumpCU\":" + std::to_string(dump_cu) + ",\"dumpSimds\":" + jarray(dump_simds, 4);
+}
+
 // A pattern test folded over its passes (hbm.h fold_passes): the HBM phase and the host link.
 struct HbmResult {
   unsigned long long bad_bits = 0, first_bad = ~0ull;
@@ -83,10 +102,8 @@ struct CusResult {
 };
 
 inline std::string cus_block(const CusResult& r) {
-  std::string per = "[";
-  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
   std::string out = "{\"expected\":" + std::to_string(r.expected) + ",\"mfmaVerified\":" + std::to_string(r.verified) +
-                    ",\"perXcd\":" + per + "]" + ",\"gemmTiles\":" + std::to_string(r.gemm_tiles) +
+                    ",\"perXcd\":" + jarray(r.per_xcd, 8) + ",\"gemmTiles\":" + std::to_string(r.gemm_tiles) +
                     ",\"badWaves\":" + std::to_string(r.bad_waves) + ",\"ok\":" +
                     jbool(r.bad_waves == 0 && r.verified >= r.expected);
   if (r.want_keys) {
@@ -160,16 +177,13 @@ struct LdsResult {
 };
 
 inline std::string lds_block(const LdsResult& r) {
-  std::string per = "[";
-  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
-  const bool none = r.first_bad == ~0ull;
   std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"bytesPerCU\":" + std::to_string(r.bytes_per_cu) +
                     ",\"patterns\":" + std::to_string(r.patterns) + ",\"salt\":" + std::to_string(r.salt) +
                     ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"cusTested\":" + std::to_string(r.tested) +
-                    ",\"cusVerified\":" + std::to_string(r.verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"cusVerified\":" + std::to_string(r.verified) + ",\"perXcd\":" + jarray(r.per_xcd, 8) +
                     ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badBits\":" + std::to_string(r.bad_bits) +
-                    ",\"firstBadCU\":" + (none ? std::string("null") : std::to_string(r.first_bad >> 32)) +
-                    ",\"firstBadOffset\":" + (none ? std::string("null") : std::to_string(r.first_bad & 0xFFFFFFFFull)) +
+                    ",\"firstBadCU\":" + first_bad_field(r.first_bad, 32, 0xFFFFFFFFull) +
+                    ",\"firstBadOffset\":" + first_bad_field(r.first_bad, 0, 0xFFFFFFFFull) +
                     ",\"ms\":" + jnum(r.ms);
   if (r.dump_cu >= 0) out += ",\"dumpCU\":" + std::to_string(r.dump_cu);
   return out + "}";
@@ -198,26 +212,19 @@ struct RegsResult {
 };
 
 inline std::string regs_block(const RegsResult& r) {
-  std::string per = "[";
-  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
-  const bool none = r.first_bad == ~0ull;
-  auto field = [&](int shift, unsigned long long mask) {
-    return none ? std::string("null") : std::to_string((r.first_bad >> shift) & mask);
-  };
+  auto field = [&](int shift, unsigned long long mask) { return first_bad_field(r.first_bad, shift, mask); };
   std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"registersPerLane\":" + std::to_string(r.registers_per_lane) +
                     ",\"workgroupsPerCU\":" + std::to_string(r.workgroups_per_cu) +
                     ",\"patterns\":" + std::to_string(r.patterns) + ",\"salt\":" + std::to_string(r.salt) +
                     ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"cusTested\":" + std::to_string(r.tested) +
                     ",\"cusVerified\":" + std::to_string(r.verified) + ",\"simdsTested\":" + std::to_string(4 * r.tested) +
-                    ",\"simdShort\":" + std::to_string(r.simd_short) + ",\"perXcd\":" + per + "]" +
+                    ",\"simdShort\":" + std::to_string(r.simd_short) + ",\"perXcd\":" + jarray(r.per_xcd, 8) +
                     ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badBits\":" + std::to_string(r.bad_bits) +
                     ",\"firstBadCU\":" + field(32, 0xFFFFFFFFull) + ",\"firstBadSimd\":" + field(16, 3) +
                     ",\"firstBadRegister\":" + field(6, 511) + ",\"firstBadLane\":" + field(0, 63) +
                     ",\"ms\":" + jnum(r.ms);
   if (!r.exclusive()) out += ",\"error\":\"RegisterKernelNotExclusive\"";
-  if (r.dump_cu >= 0)
-    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
-           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  out += dump_tail(r.dump_cu, r.dump_simds);
   return out + "}";
 }
 
@@ -251,21 +258,16 @@ struct AluResult {
 
 inline std::string alu_block(const AluResult& r) {
   static const char* const kNames[] = {"int", "f32", "f64", "f16", "lane", "trans"};
-  std::string per = "[", per_simd = "[";
-  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
-  for (int s = 0; s < 4; ++s) per_simd += (s ? "," : "") + std::to_string(r.waves_per_simd[s]);
   const bool none = r.first_bad == ~0ull;
-  auto field = [&](int shift, unsigned long long mask) {
-    return none ? std::string("null") : std::to_string((r.first_bad >> shift) & mask);
-  };
+  auto field = [&](int shift, unsigned long long mask) { return first_bad_field(r.first_bad, shift, mask); };
   const unsigned long long g = (r.first_bad >> 8) & 0xFF;
   char hex[24];
   std::snprintf(hex, sizeof hex, "\"%016llx\"", r.trans_digest);
   std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"iters\":" + std::to_string(r.iters) +
                     ",\"workgroups\":" + std::to_string(r.workgroups) + ",\"waves\":" + std::to_string(r.waves()) +
-                    ",\"wavesPerSimd\":" + per_simd + "]" + ",\"simdsTested\":" + std::to_string(r.simds_tested) +
+                    ",\"wavesPerSimd\":" + jarray(r.waves_per_simd, 4) + ",\"simdsTested\":" + std::to_string(r.simds_tested) +
                     ",\"simdsVerified\":" + std::to_string(r.simds_verified) +
-                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + jarray(r.per_xcd, 8) +
                     ",\"badWaves\":" + std::to_string(r.bad_waves) + ",\"badLanes\":" + std::to_string(r.bad_lanes) +
                     ",\"badCUs\":" + std::to_string(r.bad_cus) +
                     ",\"firstBadCU\":" + field(32, 0xFFFFFFFFull) + ",\"firstBadSimd\":" + field(16, 3) +
@@ -274,9 +276,7 @@ inline std::string alu_block(const AluResult& r) {
                     ",\"suspectCU\":" + (r.suspect < 0 ? std::string("null") : std::to_string(r.suspect >> 2)) +
                     ",\"suspectSimd\":" + (r.suspect < 0 ? std::string("null") : std::to_string(r.suspect & 3)) +
                     ",\"transDigest\":" + hex + ",\"ms\":" + jnum(r.ms);
-  if (r.dump_cu >= 0)
-    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
-           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  out += dump_tail(r.dump_cu, r.dump_simds);
   return out + "}";
 }
 
@@ -308,9 +308,6 @@ inline std::string atom_block(const AtomResult& r) {
   static const char* const kOpNames[] = {"add", "sub", "and", "or", "xor", "umin", "umax", "smin", "smax", "add_f32",
                                          "pk_add_f16", "pk_add_bf16", "add_x2", "umax_x2", "xor_x2", "add_f64", "max_f64",
                                          "add_rtn", "inc", "dec", "swap", "cas", "ticket", "returns"};
-  std::string per = "[", wgs = "[";
-  for (int x = 0; x < 8; ++x) per += (x ? "," : "") + std::to_string(r.per_xcd[x]);
-  for (int x = 0; x < 8; ++x) wgs += (x ? "," : "") + std::to_string(r.wg_per_xcd[x]);
   const bool none = r.first_bad == ~0ull;
   const unsigned long long layer = r.first_bad >> 60, op = (r.first_bad >> 52) & 0xFF, slot = (r.first_bad >> 36) & 0xFFFF,
                            xcc = (r.first_bad >> 32) & 0xF;
@@ -319,8 +316,8 @@ inline std::string atom_block(const AtomResult& r) {
   };
   std::string out = "{\"ok\":" + std::string(jbool(r.ok())) + ",\"iters\":" + std::to_string(r.iters) +
                     ",\"layers\":" + std::to_string(r.layers) + ",\"workgroups\":" + std::to_string(r.workgroups) +
-                    ",\"wgPerXcd\":" + wgs + "]" + ",\"cusTested\":" + std::to_string(r.cus_tested) +
-                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + per + "]" +
+                    ",\"wgPerXcd\":" + jarray(r.wg_per_xcd, 8) + ",\"cusTested\":" + std::to_string(r.cus_tested) +
+                    ",\"cusVerified\":" + std::to_string(r.cus_verified) + ",\"perXcd\":" + jarray(r.per_xcd, 8) +
                     ",\"badCUs\":" + std::to_string(r.bad_cus) + ",\"badWorkgroups\":" + std::to_string(r.bad_workgroups) +
                     ",\"ldsBadSlots\":" + std::to_string(r.lds_bad_slots) + ",\"l2BadSlots\":" + std::to_string(r.l2_bad_slots) +
                     ",\"devBadSlots\":" + std::to_string(r.dev_bad_slots) + ",\"badReturns\":" + std::to_string(r.bad_returns) +
@@ -331,9 +328,7 @@ inline std::string atom_block(const AtomResult& r) {
                     ",\"firstBadSlot\":" + (none ? std::string("null") : std::to_string(slot)) +
                     // lds, l2: the CU's XCD; dev: the row's XCD, 8 for the row every workgroup hits
                     ",\"firstBadXcc\":" + (none ? std::string("null") : std::to_string(xcc)) + ",\"ms\":" + jnum(r.ms);
-  if (r.dump_cu >= 0)
-    out += ",\"dumpCU\":" + std::to_string(r.dump_cu) + ",\"dumpSimds\":[" + std::to_string(r.dump_simds[0]) + "," +
-           std::to_string(r.dump_simds[1]) + "," + std::to_string(r.dump_simds[2]) + "," + std::to_string(r.dump_simds[3]) + "]";
+  out += dump_tail(r.dump_cu, r.dump_simds);
   if (r.march_ms >= 0) out += ",\"marchMs\":" + jnum(r.march_ms) + ",\"verifyMs\":" + jnum(r.verify_ms);
   return out + "}";
 }

@@ -123,6 +123,10 @@ def scenarios(tag_dir: str) -> dict[str, list[tuple]]:
         # atomics_claim_probe_cost.py --parent-lib DIR --parent-lib-copy DIR2 by hand for the default-path
         # A/B and its null pair)
         "atomics": [("atomics_claim_probe_cost", [PY, "scripts/atomics_claim_probe_cost.py"], 600, {})],
+        # the default-path A/B the *_claim_probe_cost.py scripts share; as a scenario this tree's
+        # library against itself, which is the A/B's own noise (give parent_lib_ab.py --parent-lib DIR
+        # --parent-lib-copy DIR2 by hand for this tree against a build of the parent commit)
+        "parent-ab": [("parent_lib_ab", [PY, "scripts/parent_lib_ab.py"], 900, {})],
         # the probe's two-stream shape as one hipGraph vs eager launches (r5l: not adopted)
         "graph": [("graph_events", [os.path.join(ROOT, "build", "native", "graph_events"), "1024",
                                     "15"], 120, {})],

@@ -12,10 +12,12 @@ that the default probe did not move.
     the probe's own ms per option set.
 (c) With ``--parent-lib DIR`` (a build of the parent commit's libmi355x_probe.so): child processes
     that load this tree's library or the parent's, alternating, ``--rounds`` each; a child warms up
-    and reports the p50 of 30 default probes. The margin a difference must exceed is the parent's
-    own spread: the p50 of its odd rounds against its even rounds.
+    and reports the p50 of 30 default probes. With ``--parent-lib-copy DIR2`` (a second copy of the
+    same build) the same procedure runs on the parent's library against itself: the difference of
+    that null pair is what a difference must exceed (scripts/parent_lib_ab.py).
 
-    python scripts/lds_claim_probe_cost.py [--runs 200] [--rounds 40] [--parent-lib DIR] > profiles/lds_claim_probe_cost.json
+    python scripts/lds_claim_probe_cost.py [--runs 200] [--rounds 40] [--parent-lib DIR [--parent-lib-copy DIR2]] \\
+        > profiles/lds_claim_probe_cost.json
 """
 from __future__ import annotations
 
@@ -24,40 +26,14 @@ import collections
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import parent_lib_ab  # noqa: E402  (beside this script)
 KW = dict(hbm_bytes=1 << 30, gemm_n=2048)
 FACTORS = (1, 2, 4, 8, 16)
 med = statistics.median
-
-
-def child() -> None:
-    from gpupool.ops import probe
-    probe.init()
-    for _ in range(5):
-        assert probe.run(0, **KW)["passed"]
-    print(json.dumps(med(probe.run(0, **KW)["ms"] for _ in range(30))))
-
-
-def default_path(me: list[str], parent_lib: str, rounds: int) -> dict:
-    ms: dict[str, list[float]] = {"this": [], "parent": []}
-    for r in range(rounds):
-        for which in (("this", "parent") if r % 2 == 0 else ("parent", "this")):
-            env = dict(os.environ)
-            if which == "parent":
-                env["GPUPOOL_NATIVE_DIR"] = os.path.abspath(parent_lib)
-            p = subprocess.run(me + ["--child"], env=env, capture_output=True, text=True, timeout=120, check=True)
-            ms[which].append(float(p.stdout.strip().splitlines()[-1]))
-        print(f"default path: round {r + 1}/{rounds}", file=sys.stderr, flush=True)
-    return {"what": "p50 over child processes of each child's p50 probe ms (30 default probes)",
-            "this_ms": round(med(ms["this"]), 4), "parent_ms": round(med(ms["parent"]), 4),
-            "parent_even_rounds_ms": round(med(ms["parent"][0::2]), 4),
-            "parent_odd_rounds_ms": round(med(ms["parent"][1::2]), 4),
-            "difference_ms": round(med(ms["this"]) - med(ms["parent"]), 4),
-            "margin_ms": round(abs(med(ms["parent"][0::2]) - med(ms["parent"][1::2])), 4)}
 
 
 def sweep(probe, cus: int, runs: int) -> dict:
@@ -123,15 +99,14 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=40)
-    ap.add_argument("--parent-lib", default="")
-    ap.add_argument("--child", action="store_true")
+    parent_lib_ab.add_arguments(ap)
     ap.add_argument("--default-path-only", action="store_true", help="only (c)")
     a = ap.parse_args()
     if a.child:
-        return child()
+        return parent_lib_ab.child()
     out: dict = {"probe": "hbmBytes 1 GiB x 2 patterns, gemmN 2048, two streams"}
-    if a.parent_lib:  # children first: this process has not touched the GPU yet
-        out["default_path"] = default_path([sys.executable, os.path.abspath(__file__)], a.parent_lib, a.rounds)
+    # children first: this process has not touched the GPU yet
+    out.update(parent_lib_ab.compare([sys.executable, os.path.abspath(__file__), "--child"], a))
     if a.default_path_only:
         print(json.dumps(out, indent=1))
         return

@@ -6,10 +6,11 @@ not move.
     for ``rounds`` rounds; p50 of the probe's own ms per option set.
 (b) With ``--parent-lib DIR`` (a build of the parent commit's libmi355x_probe.so): child processes
     that load this tree's library or the parent's, alternating, ``rounds`` each; a child warms up
-    and reports the p50 of 30 default probes. The margin a difference must exceed is the parent's
-    own spread: the p50 of its odd rounds against its even rounds.
+    and reports the p50 of 30 default probes. With ``--parent-lib-copy DIR2`` (a second copy of the
+    same build) the same procedure runs on the parent's library against itself: the difference of
+    that null pair is what a difference must exceed (scripts/parent_lib_ab.py).
 
-    python scripts/lowp_claim_probe_cost.py [--rounds 40] [--parent-lib DIR] > profiles/lowp_claim_probe_cost.json
+    python scripts/lowp_claim_probe_cost.py [--rounds 40] [--parent-lib DIR [--parent-lib-copy DIR2]] > profiles/lowp_claim_probe_cost.json
 """
 from __future__ import annotations
 
@@ -17,49 +18,24 @@ import argparse
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import parent_lib_ab  # noqa: E402  (beside this script)
 KW = dict(hbm_bytes=1 << 30, gemm_n=2048)
-
-
-def child() -> None:
-    from gpupool.ops import probe
-    probe.init()
-    for _ in range(5):
-        assert probe.run(0, **KW)["passed"]
-    print(json.dumps(statistics.median(probe.run(0, **KW)["ms"] for _ in range(30))))
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=40)
-    ap.add_argument("--parent-lib", default="")
-    ap.add_argument("--child", action="store_true")
+    parent_lib_ab.add_arguments(ap)
     a = ap.parse_args()
     if a.child:
-        return child()
+        return parent_lib_ab.child()
     out: dict = {"rounds": a.rounds, "probe": "hbmBytes 1 GiB x 2 patterns, gemmN 2048, two streams"}
-    if a.parent_lib:  # children first: this process has not touched the GPU yet
-        ms: dict[str, list[float]] = {"this": [], "parent": []}
-        for r in range(a.rounds):
-            for which in (("this", "parent") if r % 2 == 0 else ("parent", "this")):
-                env = dict(os.environ)
-                if which == "parent":
-                    env["GPUPOOL_NATIVE_DIR"] = os.path.abspath(a.parent_lib)
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env,
-                                   capture_output=True, text=True, timeout=120, check=True)
-                ms[which].append(float(p.stdout.strip().splitlines()[-1]))
-        med = statistics.median
-        out["default_path"] = {
-            "what": "p50 over child processes of each child's p50 probe ms (30 default probes)",
-            "this_ms": round(med(ms["this"]), 4), "parent_ms": round(med(ms["parent"]), 4),
-            "parent_even_rounds_ms": round(med(ms["parent"][0::2]), 4),
-            "parent_odd_rounds_ms": round(med(ms["parent"][1::2]), 4),
-            "difference_ms": round(med(ms["this"]) - med(ms["parent"]), 4),
-            "margin_ms": round(abs(med(ms["parent"][0::2]) - med(ms["parent"][1::2])), 4)}
+    # children first: this process has not touched the GPU yet
+    out.update(parent_lib_ab.compare([sys.executable, os.path.abspath(__file__), "--child"], a))
     from gpupool.ops import lowp, probe
     probe.init()
     sets = [(), *[(d,) for d in lowp.DTYPES], lowp.DTYPES]

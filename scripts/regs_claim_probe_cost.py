@@ -29,44 +29,14 @@ import collections
 import json
 import os
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import parent_lib_ab  # noqa: E402  (beside this script)
 KW = dict(hbm_bytes=1 << 30, gemm_n=2048)
 FACTORS = (1, 2, 4, 8, 16)
 med = statistics.median
-
-
-def child() -> None:
-    from gpupool.ops import probe
-    probe.init()
-    for _ in range(5):
-        assert probe.run(0, **KW)["passed"]
-    print(json.dumps(med(probe.run(0, **KW)["ms"] for _ in range(30))))
-
-
-def default_path(me: list[str], libs: dict[str, str], rounds: int) -> dict:
-    """``libs``: two names -> library directory ("" = this tree's). Alternating child processes."""
-    a, b = list(libs)
-    ms: dict[str, list[float]] = {a: [], b: []}
-    for r in range(rounds):
-        for which in ((a, b) if r % 2 == 0 else (b, a)):
-            env = dict(os.environ)
-            if libs[which]:
-                env["GPUPOOL_NATIVE_DIR"] = os.path.abspath(libs[which])
-            # each child is one GPU step with its own limit; a failing child ends the script
-            p = subprocess.run(me + ["--child"], env=env, capture_output=True, text=True, timeout=120, check=True)
-            ms[which].append(float(p.stdout.strip().splitlines()[-1]))
-        if (r + 1) % 10 == 0:
-            print(f"default path {a} vs {b}: round {r + 1}/{rounds}", file=sys.stderr, flush=True)
-    return {"what": "p50 over child processes of each child's p50 probe ms (30 default probes)",
-            f"{a}_ms": round(med(ms[a]), 4), f"{b}_ms": round(med(ms[b]), 4),
-            f"{b}_even_rounds_ms": round(med(ms[b][0::2]), 4),
-            f"{b}_odd_rounds_ms": round(med(ms[b][1::2]), 4),
-            "difference_ms": round(med(ms[a]) - med(ms[b]), 4),
-            "odd_even_spread_ms": round(abs(med(ms[b][0::2]) - med(ms[b][1::2])), 4)}
 
 
 def sweep(probe, cus: int, runs: int) -> dict:
@@ -140,20 +110,14 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=40)
-    ap.add_argument("--parent-lib", default="")
-    ap.add_argument("--parent-lib-copy", default="", help="a second copy of the parent's build: the null pair")
-    ap.add_argument("--child", action="store_true")
+    parent_lib_ab.add_arguments(ap)
     ap.add_argument("--default-path-only", action="store_true", help="only (c)")
     a = ap.parse_args()
     if a.child:
-        return child()
+        return parent_lib_ab.child()
     out: dict = {"probe": "hbmBytes 1 GiB x 2 patterns, gemmN 2048, two streams"}
-    me = [sys.executable, os.path.abspath(__file__)]
-    if a.parent_lib:  # children first: this process has not touched the GPU yet
-        out["default_path"] = default_path(me, {"this": "", "parent": a.parent_lib}, a.rounds)
-        if a.parent_lib_copy:
-            out["default_path_null_pair"] = default_path(me, {"parent_copy": a.parent_lib_copy, "parent": a.parent_lib},
-                                                         a.rounds)
+    # children first: this process has not touched the GPU yet
+    out.update(parent_lib_ab.compare([sys.executable, os.path.abspath(__file__), "--child"], a))
     if a.default_path_only:
         print(json.dumps(out, indent=1))
         return
